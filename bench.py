@@ -11,6 +11,11 @@ N GPUs: one process per GPU, each owns its own shard of `batch` polynomials (ind
 collective on the data path) -> weak scaling.  Timing: barrier + synchronize on both sides of exactly
 K steps, max over ranks, rank 0 prints one JSON line.
 
+A plain run does only what the headline needs: set up, ramp the clock, W warm-up steps, K timed steps, the line.
+`--full` adds everything else after the timed region: the three-launch step, per-kernel roofline figures with clock /
+power sensors, the correctness gate against the CPU oracle, the other BASELINE configs (C3 / C4 / C5) and the CPU
+baseline.  `--dump-outputs DIR` writes a fixed sample of what the last timed step computed (see dump_outputs).
+
 Launch: `python bench.py --gpus N` from a plain shell starts the N ranks itself (fresh child processes, started
 before this process touches the GPU; rendezvous on 127.0.0.1); under `python -m torch.distributed.run` the ranks
 already exist (WORLD_SIZE is set) and this file is rank code only.
@@ -153,6 +158,32 @@ def verify_against_oracle(torch, cntt, plan, n, p, batch, dev, rank, corrupt=Fal
     return {"verified": not bad, "ran": True, "checker": "oracle/cntt_oracle.c (CPU restatement), polynomials %s of a fresh seeded batch of %d, "
                                            "fused step and fwd / mul_assign_normalize / inv launches; whole batch fused == unfused"
                                            % (picks, batch), "mismatches": bad}
+
+
+DUMP_ROWS = 1024          # polynomials in the --dump-outputs sample
+DUMP_SEED = 0x5EED0D0D
+
+
+def dump_outputs(torch, a, n, batch, out_dir):
+    """--dump-outputs: a fixed, seeded sample of what the last timed step computed, i.e. of the product polynomials a caller
+    of mul_ntt_batch receives in `a` (u64 residues mod P62), as float arrays that another build's run can be compared with:
+        rows.npy             float64 (R,)        indices of the sampled polynomials (0 and batch - 1 always among them)
+        product.npy          float64 (R, n)      the residues rounded to float64 (53 of their 62 bits)
+        product_limbs16.npy  float32 (R, n, 4)   the residues exactly, as 16-bit limbs, least significant first
+    R = min(batch, DUMP_ROWS): 24 MiB at the default shape."""
+    import numpy as np
+    if batch <= DUMP_ROWS:
+        rows = np.arange(batch)
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        rows = np.sort(np.concatenate([[0, batch - 1], 1 + rng.choice(batch - 2, DUMP_ROWS - 2, replace=False)]))
+    idx = torch.from_numpy(rows).to(a.device)
+    words = a.view(batch, n).index_select(0, idx).cpu().numpy().view(np.uint64)
+    limbs = (words[..., None] >> np.array([0, 16, 32, 48], dtype=np.uint64)) & np.uint64(0xFFFF)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "product.npy"), words.astype(np.float64))
+    np.save(os.path.join(out_dir, "product_limbs16.npy"), limbs.astype(np.float32))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -584,22 +615,57 @@ def run_rank(args):
 
     # device clock ramp (untimed): the GPU idles at ~100 MHz and the package power controller needs
     # hundreds of milliseconds of sustained load to settle (profiles/r01_power_clock_lab.txt)
-    sensors = Sensors(torch, local_rank)
+    sensors = Sensors(torch, local_rank) if args.full else None
     timer.ramp(step, args.ramp_seconds)
+    # the ramp runs for a time, not a number of steps: the W + K counted steps start again from the seeded batch, so that
+    # the timed path computes the same values on every run with the same arguments (--dump-outputs)
+    cntt.fill_uniform(a, P62, 0x5EED0002 + rank * batch * N)
     for _ in range(args.warmup):
         step()
     fence()
-    sensors.phase = "timed"
+    if sensors is not None:
+        sensors.phase = "timed"
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     elapsed = time.perf_counter() - t0
-    sensors.phase = None
+    if sensors is not None:
+        sensors.phase = None
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:   # rank 0's shard: one process's output is what a caller of the path receives
+        dump_outputs(torch, a, N, batch, args.dump_outputs)
+
+    units = world * 2 * batch * args.steps        # forward + inverse transforms, all ranks
+    line = {
+        "metric": METRIC, "value": units / elapsed, "unit": "NTT/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u64", "data": "synthetic",
+        "config": {"workload": "prime64 N=1024 p=4611686018427322369 batch=%d per GPU: fwd + "
+                               "mul_assign_normalize (pre-transformed rhs) + inv, device-resident, fused in one "
+                               "kernel (cntt_prime64_mul_ntt_batch)" % batch,
+                   "polynomial_size": N, "batch_per_gpu": batch, "modulus": P62,
+                   "sharding": "independent batch shards, no collective",
+                   "launcher": "torchrun" if os.environ.get("TORCHELASTIC_RUN_ID") else
+                               ("bench.py --gpus" if world > 1 else "single process"),
+                   "dist_backend": args.dist_backend if dist is not None else None,
+                   "rccl_ranks": world if (dist is not None and args.dist_backend == "nccl") else 0},
+        "per_gpu_value": units / elapsed / world,
+    }
+    if not args.full:   # the headline is complete; everything below is --full
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(line) + "\n").encode())
+        os.close(json_fd)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # the same step as three API-faithful launches (fwd, mul_assign_normalize, inv), for reference
     timer.ramp(step_unfused, 0.3)   # its own steady state: three kernels with different power draw alternate
@@ -660,26 +726,12 @@ def run_rank(args):
     def write_line(extras, with_cpu_baseline):
         if rank != 0:
             return
-        units = world * 2 * batch * args.steps        # forward + inverse transforms, all ranks
-        out = {
-            "metric": METRIC,
-            # a number whose results do not match the oracle is not a number: value null, status 4 (see the end of run_rank)
-            "value": units / elapsed if not verdict["mismatches"] else None, "unit": "NTT/s",
+        out = dict(line)
+        # a number whose results do not match the oracle is not a number: value null, status 4 (see the end of run_rank)
+        if verdict["mismatches"]:
+            out["value"] = None
+        out.update({
             "verified": verdict["verified"], "verification": verdict,
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u64", "data": "synthetic",
-            "config": {"workload": "prime64 N=1024 p=4611686018427322369 batch=%d per GPU: fwd + "
-                                   "mul_assign_normalize (pre-transformed rhs) + inv, device-resident, fused in one "
-                                   "kernel (cntt_prime64_mul_ntt_batch)" % batch,
-                       "polynomial_size": N, "batch_per_gpu": batch, "modulus": P62,
-                       "sharding": "independent batch shards, no collective",
-                       "launcher": "torchrun" if os.environ.get("TORCHELASTIC_RUN_ID") else
-                                   ("bench.py --gpus" if world > 1 else "single process"),
-                       "dist_backend": args.dist_backend if dist is not None else None,
-                       "rccl_ranks": world if (dist is not None and args.dist_backend == "nccl") else 0},
-            "per_gpu_value": units / elapsed / world,
             "unfused_value": units / unfused, "unfused_ms_per_step": 1e3 * unfused / args.steps,
             # the three kernels of the unfused step timed alone, each at its own steady-state clock (roofline.sensors): the step
             # alternates them, so its time is their sum at the clock the MIX settles at -- no launch gap (tools/trace_gaps.py)
@@ -709,7 +761,7 @@ def run_rank(args):
                                      "inv_kernel": sensors.summary("inv"), "pointwise_kernel": sensors.summary("pointwise")}},
             "configs": extras,
             "extras_watchdog": any("watchdog" in str(c.get("error", "")) for c in extras),
-        }
+        })
         if world == 1 and not args.no_cpu_baseline and with_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(N, P62)
@@ -777,6 +829,11 @@ def main():
     ap.add_argument("--steps", type=int, default=200)   # 0.12 s timed region: long enough for an SMI sampler to see it
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=65536, help="polynomials per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the three-launch step, the per-kernel roofline legs with clock / power "
+                         "sensors, the oracle gate (`verified`), the C3 / C4 / C5 extras and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write a fixed sample of the last timed step's product polynomials to DIR/*.npy (see dump_outputs)")
     ap.add_argument("--c4-batch", type=int, default=131072,
                     help="polynomials per GPU of the C4 extra (prime64 N=16384; 131072 = 2^20 / 8 GPUs = 16 GiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -804,6 +861,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.selftest_corrupt and not args.full:
+        raise SystemExit("--selftest-corrupt tests the oracle gate, which runs with --full only")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing above has imported torch or touched HIP.
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:], args.launch_timeout))

@@ -1,12 +1,13 @@
 """bench.py contract: on a machine without a GPU it refuses to run (there is no CPU path to time); on the GPU it
-prints exactly one JSON line carrying the driver's keys, BASELINE.json's metric, and the roofline / cpu_baseline
-objects.  `--gpus N` from a plain shell starts N ranks itself; under torch.distributed.run it is rank code."""
+prints exactly one JSON line carrying the driver's keys and BASELINE.json's metric -- and, with --full, the roofline /
+cpu_baseline objects.  `--gpus N` from a plain shell starts N ranks itself; under torch.distributed.run it is rank code."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -78,8 +79,64 @@ def test_bench_refuses_without_gpu():
 
 
 @pytest.mark.gpu
+def test_plain_run_prints_the_headline_only():
+    """Without --full the line carries the headline and nothing that needs a run of its own."""
+    r = subprocess.run([sys.executable, BENCH, "--steps", "7", "--warmup", "2", "--ramp-seconds", "0.3", "--batch", "8192"],
+                       capture_output=True, text=True, cwd=ROOT, env=clean_env(), timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = one_json_line(r.stdout)
+    with open(os.path.join(ROOT, "BASELINE.json")) as f:
+        base = json.load(f)
+    assert d["metric"] == base["metric"] and d["unit"] == "NTT/s" and d["higher_is_better"] is True and d["dtype"] == "u64"
+    assert d["n_gpus"] == 1 and d["steps"] == 7 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 2 * 8192 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for key in ("roofline", "cpu_baseline", "configs", "verified", "unfused_value"):
+        assert key not in d, key
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_timed_steps_products(tmp_path, oracle):
+    """--dump-outputs: the same arguments give the same arrays, float32 / float64 only, and the arrays are what W + K steps of
+    fwd -> mul_assign_normalize(B^) -> inv compute from the seeded batch (checked on the oracle for a few sampled rows)."""
+    batch, warmup, steps, n, p = 8192, 1, 2, 1024, 4611686018427322369
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, BENCH, "--steps", str(steps), "--warmup", str(warmup), "--ramp-seconds", "0.2",
+                            "--batch", str(batch), "--dump-outputs", str(out)], capture_output=True, text=True, cwd=ROOT,
+                           env=clean_env(), timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert one_json_line(r.stdout)["steps"] == steps
+        dumps.append({f.stem: np.load(f) for f in sorted(out.glob("*.npy"))})
+    first, second = dumps
+    assert sorted(first) == ["product", "product_limbs16", "rows"]
+    assert sum(a.nbytes for a in first.values()) <= 64 * 2**20
+    for name, arr in first.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        assert np.array_equal(arr, second[name]), name
+    rows = first["rows"].astype(np.int64)
+    assert len(rows) == 1024 and rows[0] == 0 and rows[-1] == batch - 1 and np.all(np.diff(rows) > 0)
+    limbs = first["product_limbs16"].astype(np.uint64)
+    words = limbs[..., 0] | (limbs[..., 1] << np.uint64(16)) | (limbs[..., 2] << np.uint64(32)) | (limbs[..., 3] << np.uint64(48))
+    assert words.shape == (1024, n) and int(words.max()) < p
+    assert np.array_equal(first["product"], words.astype(np.float64))
+    a0 = oracle.fill_uniform(batch * n, p, 0x5EED0002, 64)
+    b0 = oracle.fill_uniform(batch * n, p, 0x5EED1002, 64)
+    plan = oracle.Plan.try_new(n, p, 64)
+    for j in (0, 1, len(rows) // 2, len(rows) - 1):
+        i = int(rows[j])
+        x, bh = a0[i * n:(i + 1) * n].copy(), b0[i * n:(i + 1) * n].copy()
+        plan.fwd(bh)
+        for _ in range(warmup + steps):
+            plan.fwd(x)
+            plan.mul_assign_normalize(x, bh)
+            plan.inv(x)
+        assert np.array_equal(words[j], x), "row %d (polynomial %d)" % (j, i)
+
+
+@pytest.mark.gpu
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--ramp-seconds",
+    r = subprocess.run([sys.executable, BENCH, "--full", "--steps", "3", "--warmup", "1", "--ramp-seconds",
                         "0.3", "--batch", "8192", "--c4-batch", "512"], capture_output=True, text=True, cwd=ROOT,
                        env=clean_env(), timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -120,7 +177,7 @@ def test_bench_json_contract():
 def test_bench_gate_closes_on_a_wrong_word():
     """The correctness gate of the printed number: with one bit of the verified batch flipped the line carries no value, says why, and the
     command fails (status 4) -- SURVEY 8(d) / BASELINE.md 3 "correctness gate before any timing is accepted"."""
-    r = subprocess.run([sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--ramp-seconds", "0.2", "--batch", "8192", "--no-extra",
+    r = subprocess.run([sys.executable, BENCH, "--full", "--steps", "2", "--warmup", "1", "--ramp-seconds", "0.2", "--batch", "8192", "--no-extra",
                         "--no-cpu-baseline", "--selftest-corrupt"], capture_output=True, text=True, cwd=ROOT, env=clean_env(), timeout=600)
     assert r.returncode == 4, (r.returncode, r.stderr[-1500:])
     d = one_json_line(r.stdout)
@@ -133,7 +190,7 @@ def test_bench_gate_closes_on_a_wrong_word():
 def test_two_ranks_on_the_gpu_box(launcher):
     """world_size 2 through both launch forms; gloo so that both ranks may share the box's single GPU.  Checks the
     multi-rank line (n_gpus, whole-job value) and the C4 legs: shard-resident and scatter -> fwd -> gather."""
-    tail = ["--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--ramp-seconds", "0.2", "--batch",
+    tail = ["--full", "--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--ramp-seconds", "0.2", "--batch",
             "4096", "--c4-batch", "64", "--no-cpu-baseline"]
     if launcher == "self":
         cmd = [sys.executable, BENCH] + tail
@@ -159,7 +216,7 @@ def test_one_rank_rccl_rehearsal():
     group comes up on the device, the timing all-reduces run on device tensors, and the C4 end-to-end leg drives
     shard.scatter_batch / gather_batch on device tensors through RCCL."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), BENCH, "--gpus", "1", "--dist-backend", "nccl", "--force-dist", "--steps", "2",
+           "--master-port", str(free_port()), BENCH, "--full", "--gpus", "1", "--dist-backend", "nccl", "--force-dist", "--steps", "2",
            "--warmup", "1", "--ramp-seconds", "0.2", "--batch", "4096", "--c4-batch", "256", "--no-cpu-baseline"]
     env = clean_env()
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -179,7 +236,7 @@ def test_line_carries_clock_and_power_and_the_watchdog_keeps_the_line():
     driver run can be told from a slow build.  (2) A leg after the timed region that does not return must not cost the headline
     line: the watchdog prints it with what finished, names the running leg, flags the line (`extras_watchdog`) and ends the rank
     -- with status 0 by default (a launcher must not discard a complete headline), 3 with --extras-strict."""
-    base = [sys.executable, BENCH, "--steps", "50", "--warmup", "2", "--ramp-seconds", "0.5", "--batch", "16384", "--c4-batch",
+    base = [sys.executable, BENCH, "--full", "--steps", "50", "--warmup", "2", "--ramp-seconds", "0.5", "--batch", "16384", "--c4-batch",
             "256", "--no-cpu-baseline"]
     r = subprocess.run(base, capture_output=True, text=True, cwd=ROOT, env=clean_env(), timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -6,7 +6,7 @@ cp concrete-ntt_amd/libcntt_hip.so /tmp/libcntt_new.so
 trap 'cp /tmp/libcntt_new.so concrete-ntt_amd/libcntt_hip.so' EXIT
 for which in new old new old; do
   if [ $which = new ]; then cp /tmp/libcntt_new.so concrete-ntt_amd/libcntt_hip.so; else cp tools/_ctrl/libcntt_hip.so concrete-ntt_amd/libcntt_hip.so; fi
-  python bench.py --no-cpu-baseline "$@" 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 c={x['config'][:2]:x for x in d['configs']}

@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # --no-cpu-baseline: the CPU leg builds the oracle through make -> sh -> cc; no such exec hops (and no 12 s of all-core
 # CPU timing) inside a profiler-initialised process tree.  Build the checker BEFORE profiling, outside the profiler.
-ARGS="$R/bench.py --gpus 1 --steps 200 --warmup 5 --no-cpu-baseline"
+ARGS="$R/bench.py --gpus 1 --steps 200 --warmup 5 --full --no-cpu-baseline"
 ZOO="$R/tools/prof_workload.py 4"
 echo "== kernel trace" | tee -a $R/gpurun_out/progress.log
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ARGS > $OUT/trace.log 2>&1; echo "trace rc=$?" | tee -a $R/gpurun_out/progress.log
