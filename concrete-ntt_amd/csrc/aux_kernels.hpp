@@ -13,7 +13,7 @@ namespace cntt {
 // ---------------------------------------------------------------------------------------------
 enum : int { PW_MUL_NORMALIZE = 0, PW_NORMALIZE = 1, PW_MUL_ACCUMULATE = 2, PW_ADD = 3 };
 
-// STREAM: the operands are larger than the 256 MiB Infinity Cache and pass through once -- non-temporal loads and stores (round 5:
+// STREAM: the operands are larger than STREAM_BYTES (host.hip, 384 MiB) and pass through once -- non-temporal loads and stores (round 5:
 // -5 % on 512 MiB operands).  Operands that fit the cache keep the default policy: with the hint a 128 MiB batch that the previous kernel
 // left in the cache is fetched from HBM again (+12 ... +17 %, profiles/r05_small_batch_ab.txt).  The launcher decides (host.hip).
 template <class T, int OP, bool STREAM = false>

@@ -410,6 +410,11 @@ static void global_stage(T *data, const TwPair<T> *tw, const ModParams<T> &P, ui
     }
 }
 
+// Working set (bytes one call reads and writes) above which the stand-alone transforms and the pointwise kernels take the
+// non-temporal policy.  384 MiB is 1.5 x the 256 MiB Infinity Cache: batches that fit the cache lost 3-17 % with the hint.
+// tests/test_gpu_multitrip_transforms.py (STREAM_BYTES) restates this number for the streaming tests.
+static constexpr size_t STREAM_BYTES = (size_t)384 << 20;
+
 // batched transform on device memory
 template <class T> static int ntt_device(const PrimePlan<T> *pl, T *d, size_t batch, bool inv, hipStream_t st) {
     if (batch == 0) return CNTT_OK;
@@ -422,9 +427,9 @@ template <class T> static int ntt_device(const PrimePlan<T> *pl, T *d, size_t ba
     const uint32_t nsub = (uint32_t)(batch << depth);
     const size_t nbfly = batch * (pl->n / 2);
     const int tcls = transform_class(pl);
-    // per-launch copy of the plan's parameters: a batch beyond the 256 MiB Infinity Cache streams (ModParams::stream, ntt_kernel.hpp)
+    // per-launch copy of the plan's parameters: a batch beyond STREAM_BYTES streams (ModParams::stream, ntt_kernel.hpp)
     ModParams<T> mp = pl->mp;
-    mp.stream = batch * pl->n * sizeof(T) > ((size_t)384 << 20) ? 1u : 0u;
+    mp.stream = batch * pl->n * sizeof(T) > STREAM_BYTES ? 1u : 0u;
     hipError_t e;
     if (depth == 1 && batch < ((size_t)1 << 32)) {
         // one size past the LDS-resident ones: a single-pass kernel exists for 64-bit words (Ntt32k), in the plan's
@@ -455,9 +460,9 @@ template <class T, int OP>
 static int pointwise_device(const PrimePlan<T> *pl, T *a, const T *b, const T *c, size_t count, hipStream_t st) {
     if (count == 0) return CNTT_OK;
     const size_t nv = count / (16 / sizeof(T)) + 1;
-    // working set of the call against the 256 MiB Infinity Cache: larger ones stream (non-temporal policy, aux_kernels.hpp)
+    // working set of the call against STREAM_BYTES: larger ones stream (non-temporal policy, aux_kernels.hpp)
     constexpr size_t NARR = OP == PW_NORMALIZE ? 1 : OP == PW_MUL_ACCUMULATE ? 3 : 2;
-    if (NARR * count * sizeof(T) > ((size_t)384 << 20))
+    if (NARR * count * sizeof(T) > STREAM_BYTES)
         hipLaunchKernelGGL((pointwise_kernel<T, OP, true>), dim3(ew_grid(nv)), dim3(256), 0, st, a, b, c, pl->mp, count);
     else
         hipLaunchKernelGGL((pointwise_kernel<T, OP, false>), dim3(ew_grid(nv)), dim3(256), 0, st, a, b, c, pl->mp, count);
