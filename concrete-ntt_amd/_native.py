@@ -132,6 +132,35 @@ class NativePlan:
     def reserve(self, batch):
         check(lib().cntt_native_reserve(self._h, batch))
 
+    # -- external product (include/cntt_ext.h: a device extension, no counterpart in the reference) ------------------------------
+    def max_terms(self):
+        """Largest nterms for which external_product_batch stays inside the kind's exact CRT range (>= 1)."""
+        return lib().cntt_native_max_terms(self._h)
+
+    def external_product_batch(self, out, terms, key_residues, nterms, nout, accumulate=False):
+        """out[b][o] (+)= sum_j terms[b][j] (*) key[j][o] in Z/2^w[X]/(X^n+1): the words of nterms*nout negacyclic_polymul calls
+        summed mod 2^w.  out: batch*nout polynomials, terms: batch*nterms, key_residues: NPRIMES buffers of nterms*nout residue
+        polynomials as fwd_batch (fwd_binary for the binary kinds) writes them for the nterms*nout key polynomials."""
+        op, oc, where, stream = self._words(out)
+        tp, tc, tw, _ = self._words(terms)
+        n = self._n
+        if nout <= 0 or nterms < 0 or oc % (n * nout) or tw != where:
+            raise Panic("out: batch*nout polynomials; terms: batch*nterms polynomials in the same memory")
+        batch = oc // (n * nout)
+        if tc != batch * nterms * n:
+            raise Panic("terms must hold batch*nterms = %d polynomials" % (batch * nterms))
+        if len(key_residues) != self.NPRIMES:
+            raise Panic("expected %d key residue buffers" % self.NPRIMES)
+        kptrs = []
+        for r in key_residues:
+            ptr, c, esz, w, _ = buffer_info(r)
+            if esz != self.RES or w != where or c != nterms * nout * n:
+                raise Panic("key residue buffers: nterms*nout residue polynomials in the memory of out")
+            kptrs.append(ptr)
+        keys = (ctypes.c_void_p * self.NPRIMES)(*kptrs)
+        check(lib().cntt_native_external_product_batch(self._h, op, tp, keys, nterms, nout, batch, 1 if accumulate else 0, where,
+                                                       stream))
+
 
 def _make(kind, nprimes, word, res, binary, doc):
     return type("Plan", (NativePlan,), {"KIND": kind, "NPRIMES": nprimes, "WORD": word, "RES": res,

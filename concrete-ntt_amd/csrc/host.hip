@@ -16,8 +16,10 @@
 #include <vector>
 
 #include "../../include/cntt.h"
+#include "../../include/cntt_ext.h"
 #include "aux_kernels.hpp"
 #include "host_math.hpp"
+#include "native_ext.hpp"
 #include "native_fused.hpp"
 #include "product_fused.hpp"
 #include "ntt_launch.hpp"
@@ -64,8 +66,8 @@ namespace {
 struct SwitchDef { const char *name; int dflt; };
 constexpr SwitchDef kSwitches[DBG_COUNT] = {
     {"fp", 1}, {"pm64", 1}, {"blk", 1}, {"mul32_blk", 1}, {"ext32_blk", 1}, {"ext_one", 1}, {"ext_split", -1}, {"native_acc", 1},
-    {"product_fused", -1}, {"plan52_via32", 1}};
-std::atomic<int> g_switch[DBG_COUNT] = {{1}, {1}, {1}, {1}, {1}, {1}, {-1}, {1}, {-1}, {1}};
+    {"product_fused", -1}, {"plan52_via32", 1}, {"native_ext", 1}};
+std::atomic<int> g_switch[DBG_COUNT] = {{1}, {1}, {1}, {1}, {1}, {1}, {-1}, {1}, {-1}, {1}, {1}};
 int switch_index(const char *key) {
     if (!key) return -1;
     for (int i = 0; i < (int)DBG_COUNT; ++i)
@@ -817,6 +819,7 @@ struct cntt_native {
     // the plan, whose 50-bit residues are visible, stay on its own primes.  Absent where the Plan32 kind does not exist (n < 32).
     std::unique_ptr<cntt_native> via32;
     std::shared_ptr<NativeCache> cache;
+    size_t max_terms = 1;   // cntt_native_max_terms (cntt_ext.h)
     size_t rbytes() const { return info.is52 ? 8 : 4; }
     uint64_t prime(int i) const { return info.is52 ? PRIMES52[i] : (uint64_t)PRIMES32[i]; }
 };
@@ -911,6 +914,105 @@ bool cntt::native_acc_enabled() {
     return debug_switch(DBG_NATIVE_ACC) != 0;   // A/B runs, parity tests
 }
 
+// Exactness bound of the external product (cntt_ext.h): the largest T with D T inside the exact range of the kind's reconstruction,
+// D = n A^2 (binary kinds: n A), A = 2^w - 1.  Unsigned big integers as little-endian 32-bit limbs: a few products and comparisons.
+namespace {
+using Big = std::vector<uint32_t>;
+void big_trim(Big &a) {
+    while (!a.empty() && a.back() == 0) a.pop_back();
+}
+Big big_of(uint64_t v) {
+    Big a{(uint32_t)v, (uint32_t)(v >> 32)};
+    big_trim(a);
+    return a;
+}
+Big big_mul(const Big &a, const Big &b) {
+    Big r(a.size() + b.size() + 1, 0);
+    for (size_t i = 0; i < a.size(); ++i) {
+        uint64_t carry = 0;
+        for (size_t j = 0; j < b.size(); ++j) {
+            const uint64_t t = (uint64_t)a[i] * b[j] + r[i + j] + carry;
+            r[i + j] = (uint32_t)t;
+            carry = t >> 32;
+        }
+        for (size_t k = i + b.size(); carry; ++k) {
+            const uint64_t t = (uint64_t)r[k] + carry;
+            r[k] = (uint32_t)t;
+            carry = t >> 32;
+        }
+    }
+    big_trim(r);
+    return r;
+}
+int big_cmp(const Big &a, const Big &b) {
+    if (a.size() != b.size()) return a.size() < b.size() ? -1 : 1;
+    for (size_t i = a.size(); i-- > 0;)
+        if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
+    return 0;
+}
+Big big_add(const Big &a, const Big &b) {
+    Big r(std::max(a.size(), b.size()) + 1, 0);
+    uint64_t carry = 0;
+    for (size_t i = 0; i < r.size(); ++i) {
+        const uint64_t t = (uint64_t)(i < a.size() ? a[i] : 0) + (i < b.size() ? b[i] : 0) + carry;
+        r[i] = (uint32_t)t;
+        carry = t >> 32;
+    }
+    big_trim(r);
+    return r;
+}
+Big big_sub(const Big &a, const Big &b) {   // a >= b
+    Big r(a);
+    int64_t borrow = 0;
+    for (size_t i = 0; i < r.size(); ++i) {
+        int64_t t = (int64_t)r[i] - (int64_t)(i < b.size() ? b[i] : 0) - borrow;
+        borrow = t < 0;
+        r[i] = (uint32_t)(t + (borrow ? ((int64_t)1 << 32) : 0));
+    }
+    big_trim(r);
+    return r;
+}
+Big big_shr(const Big &a, int s) {   // floor(a / 2^s)
+    Big r;
+    const size_t w = (size_t)s / 32;
+    const int b = s % 32;
+    for (size_t i = w; i < a.size(); ++i) {
+        const uint64_t lo = a[i], hi = i + 1 < a.size() ? a[i + 1] : 0;
+        r.push_back((uint32_t)(((hi << 32) | lo) >> b));
+    }
+    big_trim(r);
+    return r;
+}
+}  // namespace
+static size_t native_max_terms_of(const cntt_native *pl) {
+    const NativeKindInfo &I = pl->info;
+    Big M = big_of(1), Mpre = big_of(1);
+    for (int i = 0; i < I.nprimes; ++i) M = big_mul(M, big_of(pl->prime(i)));
+    const int top = I.ngroups - 1;   // the top mixed-radix digit: group ga / gb of the last group
+    for (int i = 0; i < I.nprimes; ++i)
+        if (i != I.ga[top] && i != I.gb[top]) Mpre = big_mul(Mpre, big_of(pl->prime(i)));
+    // the reference's sign rule on the top digit: exact for c in [-(M - M / Mt) / 2, (M + M / Mt) / 2 - 1]
+    Big lim = big_shr(big_sub(M, Mpre), 1);
+    const Big up = big_sub(big_shr(big_add(M, Mpre), 1), big_of(1));
+    if (big_cmp(up, lim) < 0) lim = up;
+    if (!I.is52) {   // accumulating CRT (native_fused.hpp): c <= (M - 1) / 2 and -c <= floor(M (2^27 - 3 k) / 2^28)
+        const Big a = big_shr(big_sub(M, big_of(1)), 1);
+        const Big b = big_shr(big_mul(M, big_of(((uint64_t)1 << ACC_FRAC_BITS) - 3 * (uint64_t)I.nprimes)), ACC_FRAC_BITS + 1);
+        if (big_cmp(a, lim) < 0) lim = a;
+        if (big_cmp(b, lim) < 0) lim = b;
+    }
+    Big A(I.word / 4, 0xffffffffu);   // 2^w - 1
+    Big D = big_mul(big_of(pl->n), I.binary ? A : big_mul(A, A));
+    // largest T < 2^63 with D T <= lim (bisection)
+    uint64_t lo = 0, hi = (uint64_t)1 << 63;
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (big_cmp(big_mul(D, big_of(mid)), lim) <= 0) lo = mid;
+        else hi = mid;
+    }
+    return lo < 1 ? 1 : (size_t)lo;
+}
+
 extern "C" int cntt_native_plan_new(cntt_native_kind_t kind, size_t n, cntt_native_t **out) {
     if (!out) return fail(CNTT_EINVAL, "out is NULL");
     *out = nullptr;
@@ -933,6 +1035,7 @@ extern "C" int cntt_native_plan_new(cntt_native_kind_t kind, size_t n, cntt_nati
     }
     build_crt_args(pl.get());
     build_acc_args(pl.get());
+    pl->max_terms = native_max_terms_of(pl.get());
     pl->cache = std::make_shared<NativeCache>();
     if (pl->info.is52) {
         static const cntt_native_kind_t SAME_WORDS[10] = {CNTT_NATIVE32_PLAN32, CNTT_NATIVE64_PLAN32, CNTT_NATIVE128_PLAN32,
@@ -1300,6 +1403,145 @@ extern "C" int cntt_native_negacyclic_polymul(const cntt_native_t *pl, void *pro
     if (pn != ln || pn != rn) return fail(CNTT_ELEN, "prod/lhs/rhs lengths differ");
     if (pn != pl->n) return fail(CNTT_ELEN, "assert_eq!(buf.len(), ntt_size): %zu != %zu", pn, pl->n);
     return cntt_native_negacyclic_polymul_batch(pl, prod, lhs, rhs, 1, CNTT_MEM_HOST, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// external product of the native plans (include/cntt_ext.h; no counterpart in the reference)
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t cntt_native_max_terms(const cntt_native_t *pl) { return pl ? pl->max_terms : 0; }
+
+// fused kernel (native_ext.hpp) for the Plan32 kinds at 32 <= n <= 4096; FUSED_NONE where it does not exist
+template <int KIND>
+static int native_ext_fused_try(const cntt_native *pl, void *out, const void *terms, const void *const *key, size_t nterms,
+                                size_t nout, size_t batch, bool accumulate, hipStream_t st) {
+    constexpr int KP = NativeShape<KIND>::KP;
+    FusedTables<KP> Facc{};
+    KeyPlanes K{};
+    for (int i = 0; i < KP; ++i) {
+        DeviceTables<uint32_t> t;
+        if (int rc = device_tables(pl->p32[(size_t)i].get(), &t)) return rc;
+        Facc.twf[i] = t.fwd;
+        Facc.twi[i] = t.inv;
+        Facc.P[i] = pl->mp_acc[i];
+        K.k[i] = static_cast<const uint32_t *>(key[i]);
+    }
+    const SplitArgs S = native_split_args(pl, nullptr);
+    const hipError_t e = launch_native_ext<KIND>(pl->p32[0]->logn, out, terms, K, &Facc, S, pl->acc, (uint32_t)batch, (uint32_t)nterms,
+                                                 (uint32_t)nout, accumulate, st);
+    if (e == hipSuccess) return CNTT_OK;
+    if (e != hipErrorNotSupported) return fail(CNTT_EDEVICE, "fused external product launch failed: %s", hipGetErrorString(e));
+    (void)hipGetLastError();
+    return FUSED_NONE;
+}
+static int native_ext_fused(const cntt_native *pl, void *out, const void *terms, const void *const *key, size_t nterms, size_t nout,
+                            size_t batch, bool accumulate, hipStream_t st) {
+    if (pl->info.is52 || !pl->has_acc || debug_switch(DBG_NATIVE_EXT) == 0 || batch >= ((size_t)1 << 32) ||
+        nterms >= ((size_t)1 << 32) || nout >= ((size_t)1 << 32))
+        return FUSED_NONE;
+    switch (pl->kind) {
+    case CNTT_NATIVE32_PLAN32: return native_ext_fused_try<0>(pl, out, terms, key, nterms, nout, batch, accumulate, st);
+    case CNTT_NATIVE64_PLAN32: return native_ext_fused_try<1>(pl, out, terms, key, nterms, nout, batch, accumulate, st);
+    case CNTT_NATIVE128_PLAN32: return native_ext_fused_try<2>(pl, out, terms, key, nterms, nout, batch, accumulate, st);
+    case CNTT_NATIVE_BINARY32_PLAN32: return native_ext_fused_try<3>(pl, out, terms, key, nterms, nout, batch, accumulate, st);
+    case CNTT_NATIVE_BINARY64_PLAN32: return native_ext_fused_try<4>(pl, out, terms, key, nterms, nout, batch, accumulate, st);
+    case CNTT_NATIVE_BINARY128_PLAN32: return native_ext_fused_try<5>(pl, out, terms, key, nterms, nout, batch, accumulate, st);
+    default: return FUSED_NONE;
+    }
+}
+
+// composed: residue split of all terms, one mul_accumulate chain per prime on the plane layout (its unnormalised inverse carries a
+// factor n: a normalize pass takes it off), one CRT -- into `out`, or into scratch and then added to `out` modulo 2^w
+static int native_ext_composed(const cntt_native *pl, void *out, const void *terms, const void *const *key, size_t nterms, size_t nout,
+                               size_t batch, bool accumulate, hipStream_t st) {
+    const int k = pl->info.nprimes;
+    const size_t n = pl->n, rb = pl->rbytes(), tcount = batch * nterms * n, ocount = batch * nout * n;
+    const size_t wbytes = (size_t)pl->info.word;
+    const size_t bytes = (size_t)k * (tcount + ocount) * rb + (accumulate ? ocount * wbytes : 0);
+    char *scratch = nullptr;
+    HIP_TRY(hipMallocAsync((void **)&scratch, bytes, st));
+    void *T[10], *O[10];
+    for (int i = 0; i < k; ++i) {
+        T[i] = scratch + (size_t)i * tcount * rb;
+        O[i] = scratch + ((size_t)k * tcount + (size_t)i * ocount) * rb;
+    }
+    void *crt_out = accumulate ? scratch + (size_t)k * (tcount + ocount) * rb : out;
+    int rc = native_split_device(pl, terms, T, tcount, false, st);
+    for (int i = 0; i < k && rc == CNTT_OK; ++i) {
+        if (pl->info.is52) {
+            const cntt_plan64 *sub = pl->p64[(size_t)i].get();
+            rc = external_product_device<uint64_t>(sub, (uint64_t *)O[i], (const uint64_t *)T[i], (const uint64_t *)key[i], nterms, nout,
+                                                   batch, false, st);
+            if (rc == CNTT_OK) rc = pointwise_device<uint64_t, PW_NORMALIZE>(sub, (uint64_t *)O[i], nullptr, nullptr, ocount, st);
+        } else {
+            const cntt_plan32 *sub = pl->p32[(size_t)i].get();
+            rc = external_product_device<uint32_t>(sub, (uint32_t *)O[i], (const uint32_t *)T[i], (const uint32_t *)key[i], nterms, nout,
+                                                   batch, false, st);
+            if (rc == CNTT_OK) rc = pointwise_device<uint32_t, PW_NORMALIZE>(sub, (uint32_t *)O[i], nullptr, nullptr, ocount, st);
+        }
+    }
+    if (rc == CNTT_OK) rc = native_crt_device(pl, crt_out, O, ocount, st);
+    if (rc == CNTT_OK && accumulate) {
+        if (wbytes == 4)
+            hipLaunchKernelGGL((native_word_add_kernel<uint32_t>), dim3(ew_grid(ocount)), dim3(256), 0, st, (uint32_t *)out,
+                               (const uint32_t *)crt_out, ocount);
+        else if (wbytes == 8)
+            hipLaunchKernelGGL((native_word_add_kernel<uint64_t>), dim3(ew_grid(ocount)), dim3(256), 0, st, (uint64_t *)out,
+                               (const uint64_t *)crt_out, ocount);
+        else
+            hipLaunchKernelGGL((native_word_add_kernel<Word128>), dim3(ew_grid(ocount)), dim3(256), 0, st, (Word128 *)out,
+                               (const Word128 *)crt_out, ocount);
+        if (hipGetLastError() != hipSuccess) rc = fail(CNTT_EDEVICE, "native_word_add_kernel launch failed");
+    }
+    (void)hipFreeAsync(scratch, st);
+    return rc;
+}
+
+static int native_ext_device(const cntt_native *pl, void *out, const void *terms, const void *const *key, size_t nterms, size_t nout,
+                             size_t batch, bool accumulate, hipStream_t st) {
+    if (nterms == 0) {   // the empty sum
+        if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, batch * nout * pl->n * (size_t)pl->info.word, st));
+        return CNTT_OK;
+    }
+    const int rc = native_ext_fused(pl, out, terms, key, nterms, nout, batch, accumulate, st);
+    if (rc != FUSED_NONE) return rc;
+    return native_ext_composed(pl, out, terms, key, nterms, nout, batch, accumulate, st);
+}
+
+extern "C" int cntt_native_external_product_batch(const cntt_native_t *pl, void *out, const void *terms, const void *const *key_ntt,
+                                                  size_t nterms, size_t nout, size_t batch, int accumulate, cntt_mem_t where,
+                                                  void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (nterms > pl->max_terms)
+        return fail(CNTT_EINVAL, "nterms = %zu exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range", nterms,
+                    pl->max_terms);
+    if (batch == 0 || nout == 0) return CNTT_OK;
+    if (!out) return fail(CNTT_EINVAL, "NULL argument");
+    const int k = pl->info.nprimes;
+    if (nterms) {
+        if (!terms || !key_ntt) return fail(CNTT_EINVAL, "NULL argument");
+        for (int i = 0; i < k; ++i)
+            if (!key_ntt[i]) return fail(CNTT_EINVAL, "NULL key residue plane");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) return native_ext_device(pl, out, terms, key_ntt, nterms, nout, batch, accumulate != 0, st);
+    const size_t n = pl->n, w = (size_t)pl->info.word, ob = batch * nout * n * w, tb = batch * nterms * n * w;
+    const size_t kb = nterms * nout * n * pl->rbytes();
+    DevBuf dout, dt;
+    std::vector<DevBuf> dk((size_t)k);
+    void *dkey[10];
+    if (int rc = dout.alloc(ob)) return rc;
+    if (int rc = dt.alloc(tb)) return rc;
+    for (int i = 0; i < k; ++i) {
+        if (int rc = dk[(size_t)i].alloc(kb)) return rc;
+        dkey[i] = dk[(size_t)i].p;
+        if (kb) HIP_TRY(hipMemcpyAsync(dkey[i], key_ntt[i], kb, hipMemcpyHostToDevice, st));
+    }
+    if (accumulate) HIP_TRY(hipMemcpyAsync(dout.p, out, ob, hipMemcpyHostToDevice, st));
+    if (tb) HIP_TRY(hipMemcpyAsync(dt.p, terms, tb, hipMemcpyHostToDevice, st));
+    if (int rc = native_ext_device(pl, dout.p, dt.p, dkey, nterms, nout, batch, accumulate != 0, st)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CNTT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

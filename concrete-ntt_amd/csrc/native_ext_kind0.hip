@@ -1,0 +1,3 @@
+// fused external-product kernel instantiations: native kind 0
+#define INST_KIND 0
+#include "native_ext_inst.inc"

@@ -1,0 +1,3 @@
+// fused external-product kernel instantiations: native kind 1
+#define INST_KIND 1
+#include "native_ext_inst.inc"

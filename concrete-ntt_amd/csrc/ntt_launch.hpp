@@ -21,6 +21,7 @@ enum DebugSwitch : int {
     DBG_NATIVE_ACC,     // 1 (default): accumulating-CRT whole-product kernels; 0: the parked-tile kernels
     DBG_PRODUCT_FUSED,  // -1 (default): product::Plan composed forward, fused inverse; 0 neither fused; 1 both fused
     DBG_PLAN52_VIA32,   // 1 (default): negacyclic_polymul of the Plan52 native kinds runs the Plan32 whole-product kernel; 0: composed on 50-bit primes
+    DBG_NATIVE_EXT,     // 1 (default): fused external-product kernel of the native Plan32 kinds (native_ext.hpp); 0: composed pipeline
     DBG_COUNT
 };
 int debug_switch(DebugSwitch key);
@@ -125,6 +126,13 @@ constexpr bool native_fused_acc(int kind, int logn) {
     return kind == 2 ? (logn >= 5 && logn <= 13) : kind == 5 ? (logn >= 5 && logn <= 12) : (kind >= 0 && kind <= 4 && logn >= 5 && logn <= 14);
 }
 bool native_acc_enabled();
+// Fused external product of the Plan32 kinds (native_ext.hpp): out[b][o] (+)= sum_j terms[b][j] (*) key[j][o] for 32 <= n <= 2^NATIVE_EXT_MAX_LOGN,
+// `tables_acc` the FusedTables of the accumulating CRT; hipErrorNotSupported for other sizes (the caller composes).
+struct KeyPlanes;
+constexpr int NATIVE_EXT_MAX_LOGN = 12;
+template <int KIND>
+hipError_t launch_native_ext(int logn, void *out, const void *terms, const KeyPlanes &K, const void *tables_acc, const SplitArgs &S,
+                             const AccArgs &C, uint32_t batch, uint32_t nterms, uint32_t nout, bool accumulate, hipStream_t st);
 inline int device_num_cus() {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 256;

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "cntt.h"
+#include "cntt_ext.h"
 
 namespace cntt {
 
@@ -191,6 +192,13 @@ template <cntt_native_kind_t KIND, class R, int NPRIMES, int WORD_BYTES> class N
         check(cntt_native_negacyclic_polymul_batch(h_, prod, lhs, rhs, batch, where, stream));
     }
     void reserve(size_t batch) const { check(cntt_native_reserve(h_, batch)); }
+    // external product (cntt_ext.h): out[b][o] (+)= sum_j terms[b][j] (*) key[j][o] mod 2^w, key_ntt = NPRIMES residue planes of
+    // nterms * nout forward-transformed key polynomials
+    size_t max_terms() const { return cntt_native_max_terms(h_); }
+    void external_product_batch(void *out, const void *terms, const void *const *key_ntt, size_t nterms, size_t nout, size_t batch,
+                                bool accumulate = false, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(cntt_native_external_product_batch(h_, out, terms, key_ntt, nterms, nout, batch, accumulate ? 1 : 0, where, stream));
+    }
 };
 }  // namespace detail
 
