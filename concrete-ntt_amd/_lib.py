@@ -103,6 +103,10 @@ def lib():
         # include/cntt_ext.h
         "cntt_native_external_product_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, c_int, c_int, c_vp]),
         "cntt_native_max_terms": (c_sz, [c_vp]),
+        "cntt_native_gadget_decompose_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, ctypes.c_uint, c_int, c_sz, c_int,
+                                                       c_vp]),
+        "cntt_native_external_product_decomposed_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint,
+                                                                  ctypes.c_uint, c_int, c_sz, c_sz, c_int, c_vp]),
         "cntt_product_plan_new": (c_int, [c_sz, c_u64, c_vp, c_sz, c_vp]),
         "cntt_product_plan_clone": (c_vp, [c_vp]),
         "cntt_product_plan_free": (None, [c_vp]),

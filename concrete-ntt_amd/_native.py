@@ -161,6 +161,74 @@ class NativePlan:
         check(lib().cntt_native_external_product_batch(self._h, op, tp, keys, nterms, nout, batch, 1 if accumulate else 0, where,
                                                        stream))
 
+    # -- rotation / CMux difference / signed gadget decomposition (include/cntt_gadget.h) ----------------------------------------
+    SRC_MODES = {"plain": 0, "rotate": 1, "cmux": 2}
+
+    def _src(self, polys, rot, mode):
+        """(polys pointer, word count, memory, stream, rot pointer, mode number) with the shape checks the two calls share."""
+        if mode not in self.SRC_MODES:
+            raise Panic("mode must be one of %s" % sorted(self.SRC_MODES))
+        pp, pc, where, stream = self._words(polys)
+        rp = None
+        if rot is not None:
+            rp, rc_, esz, rw, _ = buffer_info(rot)
+            if esz != 4 or rw != where:
+                raise Panic("rot: one uint32 exponent per batch element, in the memory of polys")
+            rp = (rp, rc_)
+        elif mode != "plain":
+            raise Panic("mode %r needs rot" % mode)
+        return pp, pc, where, stream, rp, self.SRC_MODES[mode]
+
+    def gadget_decompose_batch(self, terms, polys, base_log, levels, rot=None, mode="plain"):
+        """terms[b][p*levels + l-1] = signed digit l (of `levels`, base_log bits each, d_1 most significant) of the source polynomial
+        of polys[b][p]: polys itself ("plain"), X^rot[b] * polys ("rotate") or X^rot[b] * polys - polys ("cmux") in Z/2^w[X]/(X^n+1).
+        polys: batch*npolys polynomials; terms: batch*npolys*levels; npolys is taken from len(rot) = batch when rot is given, else 1."""
+        pp, pc, where, stream, rp, m = self._src(polys, rot, mode)
+        tp, tc, tw, _ = self._words(terms)
+        n = self._n
+        if levels <= 0 or base_log <= 0 or pc % n or tw != where or tc != pc * levels:
+            raise Panic("polys: batch*npolys polynomials; terms: levels times as many in the same memory; base_log, levels >= 1")
+        batch = rp[1] if rp else pc // n
+        if batch == 0 or (pc // n) % batch:
+            if pc:
+                raise Panic("polys must hold a whole number of polynomials per exponent in rot")
+            batch = 0
+        npolys = (pc // n) // batch if batch else 0
+        check(lib().cntt_native_gadget_decompose_batch(self._h, tp, pp, rp[0] if rp else None, npolys, base_log, levels, m, batch,
+                                                       where, stream))
+
+    def external_product_decomposed_batch(self, out, polys, key_residues, base_log, levels, nout, rot=None, mode="plain",
+                                          addend=None):
+        """out[b][o] = (addend[b][o] if addend is given) + sum_{p,l} digit_l(source(polys[b][p])) (*) key[p*levels + l-1][o] mod 2^w:
+        gadget_decompose_batch followed by external_product_batch, without the digits ever being stored.  out: batch*nout
+        polynomials; polys: batch*npolys; key_residues: NPRIMES buffers of npolys*levels*nout residue polynomials; addend: None, out
+        itself, polys (nout == npolys) or another buffer of out's shape.  out must not overlap polys."""
+        pp, pc, where, stream, rp, m = self._src(polys, rot, mode)
+        op, oc, ow, _ = self._words(out)
+        n = self._n
+        if nout <= 0 or levels <= 0 or base_log <= 0 or oc % (n * nout) or ow != where:
+            raise Panic("out: batch*nout polynomials in the memory of polys; base_log, levels, nout >= 1")
+        batch = oc // (n * nout)
+        if (batch == 0 and pc) or (batch and pc % (batch * n)) or (rp and rp[1] != batch):
+            raise Panic("polys must hold batch*npolys polynomials and rot one exponent per batch element")
+        npolys = pc // (batch * n) if batch else 0
+        ap = None
+        if addend is not None:
+            ap, ac, aw, _ = self._words(addend)
+            if ac != oc or aw != where:
+                raise Panic("addend must have the shape and the memory of out")
+        if len(key_residues) != self.NPRIMES:
+            raise Panic("expected %d key residue buffers" % self.NPRIMES)
+        kptrs = []
+        for r in key_residues:
+            ptr, c, esz, w, _ = buffer_info(r)
+            if esz != self.RES or w != where or c != npolys * levels * nout * n:
+                raise Panic("key residue buffers: npolys*levels*nout residue polynomials in the memory of out")
+            kptrs.append(ptr)
+        keys = (ctypes.c_void_p * self.NPRIMES)(*kptrs)
+        check(lib().cntt_native_external_product_decomposed_batch(self._h, op, pp, rp[0] if rp else None, ap, keys, npolys, base_log,
+                                                                  levels, m, nout, batch, where, stream))
+
 
 def _make(kind, nprimes, word, res, binary, doc):
     return type("Plan", (NativePlan,), {"KIND": kind, "NPRIMES": nprimes, "WORD": word, "RES": res,

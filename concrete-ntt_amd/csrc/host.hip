@@ -20,6 +20,7 @@
 #include "aux_kernels.hpp"
 #include "host_math.hpp"
 #include "native_ext.hpp"
+#include "native_gadget.hpp"
 #include "native_fused.hpp"
 #include "product_fused.hpp"
 #include "ntt_launch.hpp"
@@ -66,8 +67,8 @@ namespace {
 struct SwitchDef { const char *name; int dflt; };
 constexpr SwitchDef kSwitches[DBG_COUNT] = {
     {"fp", 1}, {"pm64", 1}, {"blk", 1}, {"mul32_blk", 1}, {"ext32_blk", 1}, {"ext_one", 1}, {"ext_split", -1}, {"native_acc", 1},
-    {"product_fused", -1}, {"plan52_via32", 1}, {"native_ext", 1}};
-std::atomic<int> g_switch[DBG_COUNT] = {{1}, {1}, {1}, {1}, {1}, {1}, {-1}, {1}, {-1}, {1}, {1}};
+    {"product_fused", -1}, {"plan52_via32", 1}, {"native_ext", 1}, {"native_gadget", 0}};
+std::atomic<int> g_switch[DBG_COUNT] = {{1}, {1}, {1}, {1}, {1}, {1}, {-1}, {1}, {-1}, {1}, {1}, {0}};
 int switch_index(const char *key) {
     if (!key) return -1;
     for (int i = 0; i < (int)DBG_COUNT; ++i)
@@ -1539,6 +1540,239 @@ extern "C" int cntt_native_external_product_batch(const cntt_native_t *pl, void 
     if (accumulate) HIP_TRY(hipMemcpyAsync(dout.p, out, ob, hipMemcpyHostToDevice, st));
     if (tb) HIP_TRY(hipMemcpyAsync(dt.p, terms, tb, hipMemcpyHostToDevice, st));
     if (int rc = native_ext_device(pl, dout.p, dt.p, dkey, nterms, nout, batch, accumulate != 0, st)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CNTT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// rotation / CMux difference / signed gadget decomposition and the external product on undecomposed polynomials
+// (include/cntt_gadget.h, native_gadget.hpp)
+// ---------------------------------------------------------------------------------------------
+static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return abytes && bbytes && x < y + bbytes && y < x + abytes;
+}
+// the checks the two calls share; wbits = word width of the kind
+static int gadget_check(const cntt_native *pl, unsigned base_log, unsigned levels, int mode, const uint32_t *rot) {
+    const unsigned wbits = 8u * (unsigned)pl->info.word;
+    if (base_log == 0) return fail(CNTT_EINVAL, "base_log is 0");
+    if (levels == 0) return fail(CNTT_EINVAL, "levels is 0");
+    if ((uint64_t)base_log * levels > wbits) return fail(CNTT_EINVAL, "base_log * levels = %u * %u exceeds the word width %u", base_log, levels, wbits);
+    if (mode != CNTT_SRC_PLAIN && mode != CNTT_SRC_ROTATE && mode != CNTT_SRC_CMUX) return fail(CNTT_EINVAL, "src_mode %d is not a cntt_src_mode_t", mode);
+    if (mode != CNTT_SRC_PLAIN && !rot) return fail(CNTT_EINVAL, "rot is NULL and src_mode reads it");
+    return CNTT_OK;
+}
+// off = 2^(s-1) + K 2^s mod 2^w, K = sum_l (B/2) B^(levels-l), s = w - base_log levels (native_gadget.hpp)
+static u128 gadget_offset(unsigned wbits, unsigned base_log, unsigned levels) {
+    const unsigned s = wbits - base_log * levels;
+    u128 off = s ? (u128)1 << (s - 1) : 0;
+    for (unsigned l = 1; l <= levels; ++l) off += (u128)1 << (wbits - base_log * l + base_log - 1);   // (B/2) B^(levels-l) 2^s
+    return off;   // (wbits < 128: the caller truncates)
+}
+template <class W> static W word_from(u128 v) { return (W)v; }
+template <> Word128 word_from<Word128>(u128 v) { return Word128{(uint64_t)v, (uint64_t)(v >> 64)}; }
+
+template <class W>
+static int gadget_launch_w(void *terms, const void *polys, const uint32_t *rot, size_t npolys, unsigned base_log, unsigned levels, int mode,
+                           size_t batch, int logn, hipStream_t st) {
+    constexpr unsigned WB = sizeof(W) * 8;
+    GadgetConst<W> G{};
+    G.off = word_from<W>(gadget_offset(WB, base_log, levels));
+    G.mask = word_from<W>(base_log == 128 ? ~(u128)0 : ((u128)1 << base_log) - 1);
+    G.half = word_from<W>((u128)1 << (base_log - 1));
+    G.base_log = base_log;
+    G.levels = levels;
+    G.npolys = (uint32_t)npolys;
+    G.rotated = mode != CNTT_SRC_PLAIN;
+    G.cmux = mode == CNTT_SRC_CMUX;
+    const size_t total = batch * npolys, n = (size_t)1 << logn;
+    const unsigned grid = ew_grid(total * n * sizeof(W) / 16);
+    // the terms against STREAM_BYTES, as the pointwise kernels decide it: larger ones pass through once (non-temporal stores)
+    if (total * levels * n * sizeof(W) > STREAM_BYTES)
+        hipLaunchKernelGGL((native_gadget_kernel<W, true>), dim3(grid), dim3(256), 0, st, (W *)terms, (const W *)polys, rot, G, (uint32_t)logn, total);
+    else
+        hipLaunchKernelGGL((native_gadget_kernel<W, false>), dim3(grid), dim3(256), 0, st, (W *)terms, (const W *)polys, rot, G, (uint32_t)logn, total);
+    if (hipGetLastError() != hipSuccess) return fail(CNTT_EDEVICE, "native_gadget_kernel launch failed");
+    return CNTT_OK;
+}
+static int native_logn(const cntt_native *pl) {
+    int logn = 0;
+    while (((size_t)1 << logn) < pl->n) ++logn;
+    return logn;
+}
+static int native_gadget_device(const cntt_native *pl, void *terms, const void *polys, const uint32_t *rot, size_t npolys, unsigned base_log,
+                                unsigned levels, int mode, size_t batch, hipStream_t st) {
+    if (batch == 0 || npolys == 0) return CNTT_OK;
+    if (npolys >= ((size_t)1 << 32)) return fail(CNTT_EINVAL, "npolys too large");
+    const int logn = native_logn(pl);
+    switch (pl->info.word) {
+    case 4: return gadget_launch_w<uint32_t>(terms, polys, rot, npolys, base_log, levels, mode, batch, logn, st);
+    case 8: return gadget_launch_w<uint64_t>(terms, polys, rot, npolys, base_log, levels, mode, batch, logn, st);
+    default: return gadget_launch_w<Word128>(terms, polys, rot, npolys, base_log, levels, mode, batch, logn, st);
+    }
+}
+// host path: the exponents are in reach, so a >= 2n is an error there
+static int gadget_check_rot_host(const cntt_native *pl, const uint32_t *rot, int mode, size_t batch) {
+    if (mode == CNTT_SRC_PLAIN) return CNTT_OK;
+    for (size_t b = 0; b < batch; ++b)
+        if ((size_t)rot[b] >= 2 * pl->n) return fail(CNTT_EINVAL, "rot[%zu] = %u is not below 2n = %zu", b, rot[b], 2 * pl->n);
+    return CNTT_OK;
+}
+
+extern "C" int cntt_native_gadget_decompose_batch(const cntt_native_t *pl, void *terms, const void *polys, const uint32_t *rot,
+                                                  size_t npolys, unsigned base_log, unsigned levels, cntt_src_mode_t src_mode, size_t batch,
+                                                  cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (int rc = gadget_check(pl, base_log, levels, (int)src_mode, rot)) return rc;
+    if (batch == 0 || npolys == 0) return CNTT_OK;
+    if (!terms || !polys) return fail(CNTT_EINVAL, "NULL argument");
+    const size_t pb = batch * npolys * pl->n * (size_t)pl->info.word, tb = pb * levels;
+    if (ranges_overlap(terms, tb, polys, pb)) return fail(CNTT_EINVAL, "terms overlaps polys");
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) return native_gadget_device(pl, terms, polys, rot, npolys, base_log, levels, (int)src_mode, batch, st);
+    if (int rc = gadget_check_rot_host(pl, rot, (int)src_mode, batch)) return rc;
+    DevBuf dt, dp, dr;
+    if (int rc = dt.alloc(tb)) return rc;
+    if (int rc = dp.alloc(pb)) return rc;
+    if (int rc = dr.alloc(batch * sizeof(uint32_t))) return rc;
+    HIP_TRY(hipMemcpyAsync(dp.p, polys, pb, hipMemcpyHostToDevice, st));
+    if (src_mode != CNTT_SRC_PLAIN) HIP_TRY(hipMemcpyAsync(dr.p, rot, batch * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (int rc = native_gadget_device(pl, dt.p, dp.p, (const uint32_t *)dr.p, npolys, base_log, levels, (int)src_mode, batch, st)) return rc;
+    HIP_TRY(hipMemcpyAsync(terms, dt.p, tb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CNTT_OK;
+}
+
+// fused kernel (native_gadget.hpp): the 32- and 64-bit Plan32 kinds at 32 <= n <= 4096, base_log <= 31; FUSED_NONE elsewhere
+template <int KIND>
+static int native_ext_gadget_try(const cntt_native *pl, void *out, const GadgetCall &G, const void *const *key, size_t nout, size_t batch,
+                                 hipStream_t st) {
+    constexpr int KP = NativeShape<KIND>::KP;
+    FusedTables<KP> Facc{};
+    KeyPlanes K{};
+    for (int i = 0; i < KP; ++i) {
+        DeviceTables<uint32_t> t;
+        if (int rc = device_tables(pl->p32[(size_t)i].get(), &t)) return rc;
+        Facc.twf[i] = t.fwd;
+        Facc.twi[i] = t.inv;
+        Facc.P[i] = pl->mp_acc[i];
+        K.k[i] = static_cast<const uint32_t *>(key[i]);
+    }
+    const SplitArgs S = native_split_args(pl, nullptr);
+    const hipError_t e = launch_native_ext_gadget<KIND>(pl->p32[0]->logn, out, G, K, &Facc, S, pl->acc, (uint32_t)batch, (uint32_t)nout, st);
+    if (e == hipSuccess) return CNTT_OK;
+    if (e != hipErrorNotSupported) return fail(CNTT_EDEVICE, "fused decomposing external product launch failed: %s", hipGetErrorString(e));
+    (void)hipGetLastError();
+    return FUSED_NONE;
+}
+static int native_ext_gadget_fused(const cntt_native *pl, void *out, const GadgetCall &G, const void *const *key, size_t nout, size_t batch,
+                                   hipStream_t st) {
+    if (pl->info.is52 || !pl->has_acc || pl->info.word > 8 || G.base_log > 31 || debug_switch(DBG_NATIVE_GADGET) <= 0 ||
+        batch >= ((size_t)1 << 32) || nout >= ((size_t)1 << 32))
+        return FUSED_NONE;
+    switch (pl->kind) {
+    case CNTT_NATIVE32_PLAN32: return native_ext_gadget_try<0>(pl, out, G, key, nout, batch, st);
+    case CNTT_NATIVE64_PLAN32: return native_ext_gadget_try<1>(pl, out, G, key, nout, batch, st);
+    case CNTT_NATIVE_BINARY32_PLAN32: return native_ext_gadget_try<3>(pl, out, G, key, nout, batch, st);
+    case CNTT_NATIVE_BINARY64_PLAN32: return native_ext_gadget_try<4>(pl, out, G, key, nout, batch, st);
+    default: return FUSED_NONE;
+    }
+}
+template <class W> static void word_add_launch(void *a, const void *b, size_t count, hipStream_t st) {
+    hipLaunchKernelGGL((native_word_add_kernel<W>), dim3(ew_grid(count)), dim3(256), 0, st, (W *)a, (const W *)b, count);
+}
+// addend: nullptr, `out`, or a buffer that does not overlap out (checked by the caller)
+static int native_ext_gadget_device(const cntt_native *pl, void *out, const void *polys, const uint32_t *rot, const void *addend,
+                                    const void *const *key, size_t npolys, unsigned base_log, unsigned levels, int mode, size_t nout,
+                                    size_t batch, hipStream_t st) {
+    const size_t n = pl->n, w = (size_t)pl->info.word, ocount = batch * nout * n, nterms = npolys * levels;
+    if (nterms == 0) {   // the empty sum: out = addend, or zero
+        if (!addend) HIP_TRY(hipMemsetAsync(out, 0, ocount * w, st));
+        else if (addend != out) HIP_TRY(hipMemcpyAsync(out, addend, ocount * w, hipMemcpyDeviceToDevice, st));
+        return CNTT_OK;
+    }
+    GadgetCall G{};
+    G.polys = polys;
+    G.rot = mode == CNTT_SRC_PLAIN ? nullptr : rot;
+    G.addend = addend == out ? nullptr : addend;
+    G.off = w <= 8 ? (uint64_t)gadget_offset(8u * (unsigned)w, base_log, levels) : 0;   // (the fused kernel: u32 / u64 words)
+    G.npolys = (uint32_t)npolys;
+    G.levels = levels;
+    G.base_log = base_log;
+    G.cmux = mode == CNTT_SRC_CMUX;
+    G.add_out = addend == out;
+    const int rc = native_ext_gadget_fused(pl, out, G, key, nout, batch, st);
+    if (rc != FUSED_NONE) return rc;
+    // composed: the digits into stream-ordered scratch, the external product on them, then the addend
+    char *scratch = nullptr;
+    HIP_TRY(hipMallocAsync((void **)&scratch, batch * nterms * n * w, st));
+    int rc2 = native_gadget_device(pl, scratch, polys, rot, npolys, base_log, levels, mode, batch, st);
+    if (rc2 == CNTT_OK) rc2 = native_ext_device(pl, out, scratch, key, nterms, nout, batch, addend == out, st);
+    if (rc2 == CNTT_OK && addend && addend != out) {
+        if (w == 4) word_add_launch<uint32_t>(out, addend, ocount, st);
+        else if (w == 8) word_add_launch<uint64_t>(out, addend, ocount, st);
+        else word_add_launch<Word128>(out, addend, ocount, st);
+        if (hipGetLastError() != hipSuccess) rc2 = fail(CNTT_EDEVICE, "native_word_add_kernel launch failed");
+    }
+    (void)hipFreeAsync(scratch, st);
+    return rc2;
+}
+
+extern "C" int cntt_native_external_product_decomposed_batch(const cntt_native_t *pl, void *out, const void *polys, const uint32_t *rot,
+                                                             const void *addend, const void *const *key_ntt, size_t npolys,
+                                                             unsigned base_log, unsigned levels, cntt_src_mode_t src_mode, size_t nout,
+                                                             size_t batch, cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (int rc = gadget_check(pl, base_log, levels, (int)src_mode, rot)) return rc;
+    const size_t nterms = npolys * levels;
+    if (nterms > pl->max_terms)
+        return fail(CNTT_EINVAL, "npolys * levels = %zu exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range", nterms,
+                    pl->max_terms);
+    if (batch == 0 || nout == 0) return CNTT_OK;
+    if (!out) return fail(CNTT_EINVAL, "out is NULL");
+    const int k = pl->info.nprimes;
+    const size_t n = pl->n, w = (size_t)pl->info.word, ob = batch * nout * n * w, pb = batch * npolys * n * w;
+    if (nterms) {
+        if (!polys || !key_ntt) return fail(CNTT_EINVAL, "NULL argument");
+        for (int i = 0; i < k; ++i)
+            if (!key_ntt[i]) return fail(CNTT_EINVAL, "NULL key residue plane");
+        if (ranges_overlap(out, ob, polys, pb)) return fail(CNTT_EINVAL, "out overlaps polys");
+    }
+    if (addend && addend != out && ranges_overlap(out, ob, addend, ob)) return fail(CNTT_EINVAL, "addend overlaps out without being out");
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE)
+        return native_ext_gadget_device(pl, out, polys, rot, addend, key_ntt, npolys, base_log, levels, (int)src_mode, nout, batch, st);
+    if (nterms)
+        if (int rc = gadget_check_rot_host(pl, rot, (int)src_mode, batch)) return rc;
+    const size_t kb = nterms * nout * n * pl->rbytes();
+    DevBuf dout, dp, dr, da;
+    std::vector<DevBuf> dk((size_t)k);
+    void *dkey[10];
+    if (int rc = dout.alloc(ob)) return rc;
+    if (int rc = dp.alloc(pb)) return rc;
+    if (int rc = dr.alloc(batch * sizeof(uint32_t))) return rc;
+    for (int i = 0; i < k; ++i) {
+        if (int rc = dk[(size_t)i].alloc(kb)) return rc;
+        dkey[i] = dk[(size_t)i].p;
+        if (kb) HIP_TRY(hipMemcpyAsync(dkey[i], key_ntt[i], kb, hipMemcpyHostToDevice, st));
+    }
+    if (pb) HIP_TRY(hipMemcpyAsync(dp.p, polys, pb, hipMemcpyHostToDevice, st));
+    if (nterms && src_mode != CNTT_SRC_PLAIN) HIP_TRY(hipMemcpyAsync(dr.p, rot, batch * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    const void *dadd = nullptr;
+    if (addend == out) {
+        HIP_TRY(hipMemcpyAsync(dout.p, out, ob, hipMemcpyHostToDevice, st));
+        dadd = dout.p;
+    } else if (addend && addend == polys && pb == ob) {
+        dadd = dp.p;
+    } else if (addend) {
+        if (int rc = da.alloc(ob)) return rc;
+        HIP_TRY(hipMemcpyAsync(da.p, addend, ob, hipMemcpyHostToDevice, st));
+        dadd = da.p;
+    }
+    if (int rc = native_ext_gadget_device(pl, dout.p, dp.p, (const uint32_t *)dr.p, dadd, dkey, npolys, base_log, levels, (int)src_mode, nout,
+                                          batch, st))
+        return rc;
     HIP_TRY(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return CNTT_OK;

@@ -22,6 +22,7 @@ enum DebugSwitch : int {
     DBG_PRODUCT_FUSED,  // -1 (default): product::Plan composed forward, fused inverse; 0 neither fused; 1 both fused
     DBG_PLAN52_VIA32,   // 1 (default): negacyclic_polymul of the Plan52 native kinds runs the Plan32 whole-product kernel; 0: composed on 50-bit primes
     DBG_NATIVE_EXT,     // 1 (default): fused external-product kernel of the native Plan32 kinds (native_ext.hpp); 0: composed pipeline
+    DBG_NATIVE_GADGET,  // 0 (default): external product on undecomposed polynomials = decompose, then the external product; 1: the fused kernel (native_gadget.hpp), measured slower
     DBG_COUNT
 };
 int debug_switch(DebugSwitch key);
@@ -133,6 +134,20 @@ constexpr int NATIVE_EXT_MAX_LOGN = 12;
 template <int KIND>
 hipError_t launch_native_ext(int logn, void *out, const void *terms, const KeyPlanes &K, const void *tables_acc, const SplitArgs &S,
                              const AccArgs &C, uint32_t batch, uint32_t nterms, uint32_t nout, bool accumulate, hipStream_t st);
+// The same on undecomposed polynomials (native_gadget.hpp): the terms are the signed gadget digits of the rotated / CMux source
+// polynomials, derived while loading.  u32 / u64 words (KIND 0, 1, 3, 4), base_log <= 31; hipErrorNotSupported otherwise.
+struct GadgetCall {
+    const void *polys;     // batch x npolys polynomials
+    const uint32_t *rot;   // one exponent per element, taken mod 2n; nullptr: no rotation
+    const void *addend;    // nullptr, or batch x nout polynomials that do not overlap out
+    uint64_t off;          // 2^(s-1) + K 2^s of the decomposition (native_gadget.hpp)
+    uint32_t npolys, levels, base_log;
+    uint32_t cmux;         // subtract the unrotated polynomial
+    uint32_t add_out;      // the addend is `out` itself
+};
+template <int KIND>
+hipError_t launch_native_ext_gadget(int logn, void *out, const GadgetCall &G, const KeyPlanes &K, const void *tables_acc,
+                                    const SplitArgs &S, const AccArgs &C, uint32_t batch, uint32_t nout, hipStream_t st);
 inline int device_num_cus() {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 256;

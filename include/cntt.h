@@ -94,6 +94,8 @@ int cntt_shard_bounds(size_t batch, int world, int rank, size_t *begin, size_t *
 /*   "product_fused"    -1     product::Plan: composed forward + fused inverse; 0 neither fused; 1 both                               */
 /*   "plan52_via32"      1     negacyclic_polymul of the Plan52 native kinds through the Plan32 whole-product kernel; 0: 50-bit primes */
 /*   "native_ext"        1     cntt_native_external_product_batch (cntt_ext.h) through the fused kernel; 0: the composed pipeline     */
+/*   "native_gadget"     0     cntt_native_external_product_decomposed_batch (cntt_ext.h): decompose, then                            */
+/*                             cntt_native_external_product_batch; 1: the fused kernel (measured slower, kept for A/B runs)           */
 /* value -1 restores a switch's default; key "reset" restores all.  Process-wide, thread-safe (atomics); the two class switches are    */
 /* recorded in the plan at creation (cntt_prime*_plan_info().arith_class reports the class in use), the others are read per call.      */
 /* ------------------------------------------------------------------------------------- */

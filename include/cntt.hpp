@@ -199,6 +199,19 @@ template <cntt_native_kind_t KIND, class R, int NPRIMES, int WORD_BYTES> class N
                                 bool accumulate = false, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
         check(cntt_native_external_product_batch(h_, out, terms, key_ntt, nterms, nout, batch, accumulate ? 1 : 0, where, stream));
     }
+    // signed gadget digits of polys, X^rot polys or X^rot polys - polys (cntt_gadget.h), and the external product that derives them
+    // while loading: out = addend + sum_{p,l} digit_l(source(polys[p])) (*) key[p * levels + l - 1][o]
+    void gadget_decompose_batch(void *terms, const void *polys, const uint32_t *rot, size_t npolys, unsigned base_log, unsigned levels,
+                                cntt_src_mode_t mode, size_t batch, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(cntt_native_gadget_decompose_batch(h_, terms, polys, rot, npolys, base_log, levels, mode, batch, where, stream));
+    }
+    void external_product_decomposed_batch(void *out, const void *polys, const uint32_t *rot, const void *addend,
+                                           const void *const *key_ntt, size_t npolys, unsigned base_log, unsigned levels,
+                                           cntt_src_mode_t mode, size_t nout, size_t batch, cntt_mem_t where = CNTT_MEM_DEVICE,
+                                           void *stream = nullptr) const {
+        check(cntt_native_external_product_decomposed_batch(h_, out, polys, rot, addend, key_ntt, npolys, base_log, levels, mode, nout,
+                                                            batch, where, stream));
+    }
 };
 }  // namespace detail
 

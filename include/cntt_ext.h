@@ -50,4 +50,9 @@ size_t cntt_native_max_terms(const cntt_native_t *plan);
 }
 #endif
 
+/* Rotation / CMux difference / signed gadget decomposition (cntt_src_mode_t, cntt_native_gadget_decompose_batch) and the external
+ * product on undecomposed polynomials (cntt_native_external_product_decomposed_batch) are declared here through a file of their own,
+ * which carries their semantics. */
+#include "cntt_gadget.h"
+
 #endif /* CNTT_EXT_H */
