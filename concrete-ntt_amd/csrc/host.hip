@@ -21,6 +21,7 @@
 #include "host_math.hpp"
 #include "native_ext.hpp"
 #include "native_gadget.hpp"
+#include "native_pbs.hpp"
 #include "native_fused.hpp"
 #include "product_fused.hpp"
 #include "ntt_launch.hpp"
@@ -1774,6 +1775,238 @@ extern "C" int cntt_native_external_product_decomposed_batch(const cntt_native_t
                                           batch, st))
         return rc;
     HIP_TRY(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CNTT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// programmable bootstrap: modulus switch, blind rotation in place, sample extraction (include/cntt_pbs.h, native_pbs.hpp)
+// ---------------------------------------------------------------------------------------------
+static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+// the three parts of the workspace, in bytes and in this order (cntt_pbs.h states the formula)
+struct PbsSizes {
+    size_t digits, rot, acc;
+    size_t total() const { return up256(digits) + up256(rot) + up256(acc); }
+};
+static PbsSizes pbs_sizes(const cntt_native *pl, size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) {
+    const size_t pb = batch * (glwe_dim + 1) * pl->n * (size_t)pl->info.word;
+    return PbsSizes{pb * levels, (lwe_dim + 1) * batch * sizeof(uint32_t), pb};
+}
+extern "C" size_t cntt_native_pbs_workspace_bytes(const cntt_native_t *pl, size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) {
+    return pl ? pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch).total() : 0;
+}
+
+static int native_modswitch_device(const cntt_native *pl, uint32_t *rot_t, const void *lwe, size_t lwe_dim, size_t batch, hipStream_t st) {
+    if (native_logn(pl) > 30) return fail(CNTT_EINVAL, "ntt_size too large for the modulus switch");   // ms() reads the top 32 bits
+    const size_t tiles = ((lwe_dim + PBS_TILE) / PBS_TILE) * ((batch + PBS_TILE - 1) / PBS_TILE);
+    const hipError_t e = launch_native_lwe_modswitch(pl->info.word, rot_t, lwe, native_logn(pl), lwe_dim, batch, ew_grid(tiles * 256), st);
+    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_lwe_modswitch_kernel launch failed: %s", hipGetErrorString(e));
+    return CNTT_OK;
+}
+static int native_extract_device(const cntt_native *pl, void *lwe_out, const void *glwe, size_t glwe_dim, size_t index, size_t batch,
+                                 hipStream_t st) {
+    const hipError_t e = launch_native_sample_extract(pl->info.word, lwe_out, glwe, native_logn(pl), glwe_dim, (uint32_t)index, batch,
+                                                      ew_grid(batch * (glwe_dim * pl->n + 1)), st);
+    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_sample_extract_kernel launch failed: %s", hipGetErrorString(e));
+    return CNTT_OK;
+}
+// acc = X^(body row of rot_t) lut, then lwe_dim times decomposition (CMux difference) into `digits` and the external product accumulating
+// into acc.  In place is sound: the digits are complete before the product starts (stream order), the product reads only the digits and
+// the key, and each of its launches of two outputs reads and writes only its own outputs.
+static int native_blind_rotate_device(const cntt_native *pl, void *acc, const void *lut, bool lut_per_element, const uint32_t *rot_t,
+                                      const void *const *bsk, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels,
+                                      size_t batch, void *digits, hipStream_t st) {
+    const size_t npolys = glwe_dim + 1, nterms = npolys * levels, n = pl->n, w = (size_t)pl->info.word;
+    const size_t slice = nterms * npolys * n * pl->rbytes();   // one iteration's key, bytes per plane
+    const hipError_t e = launch_native_pbs_init(pl->info.word, acc, lut, rot_t + lwe_dim * batch, native_logn(pl), (uint32_t)npolys,
+                                                lut_per_element, batch, batch * npolys * n * w > STREAM_BYTES,
+                                                ew_grid(batch * npolys * n * w / 16), st);
+    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_pbs_init_kernel launch failed: %s", hipGetErrorString(e));
+    const int k = pl->info.nprimes;
+    const void *key[10];
+    for (size_t i = 0; i < lwe_dim; ++i) {
+        for (int j = 0; j < k; ++j) key[j] = static_cast<const char *>(bsk[j]) + i * slice;
+        if (int rc = native_gadget_device(pl, digits, acc, rot_t + i * batch, npolys, base_log, levels, CNTT_SRC_CMUX, batch, st)) return rc;
+        if (int rc = native_ext_device(pl, acc, digits, key, nterms, npolys, batch, true, st)) return rc;
+    }
+    return CNTT_OK;
+}
+
+extern "C" int cntt_native_lwe_modswitch_batch(const cntt_native_t *pl, uint32_t *rot_t, const void *lwe, size_t lwe_dim, size_t batch,
+                                               cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (batch == 0) return CNTT_OK;
+    if (!rot_t) return fail(CNTT_EINVAL, "rot_t is NULL");
+    if (!lwe) return fail(CNTT_EINVAL, "lwe is NULL");
+    const size_t rb = (lwe_dim + 1) * batch * sizeof(uint32_t), lb = (lwe_dim + 1) * batch * (size_t)pl->info.word;
+    if (ranges_overlap(rot_t, rb, lwe, lb)) return fail(CNTT_EINVAL, "rot_t overlaps lwe");
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) return native_modswitch_device(pl, rot_t, lwe, lwe_dim, batch, st);
+    DevBuf dr, dl;
+    if (int rc = dr.alloc(rb)) return rc;
+    if (int rc = dl.alloc(lb)) return rc;
+    HIP_TRY(hipMemcpyAsync(dl.p, lwe, lb, hipMemcpyHostToDevice, st));
+    if (int rc = native_modswitch_device(pl, (uint32_t *)dr.p, dl.p, lwe_dim, batch, st)) return rc;
+    HIP_TRY(hipMemcpyAsync(rot_t, dr.p, rb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CNTT_OK;
+}
+
+extern "C" int cntt_native_sample_extract_batch(const cntt_native_t *pl, void *lwe_out, const void *glwe, size_t glwe_dim, size_t index,
+                                                size_t batch, cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (index >= pl->n) return fail(CNTT_EINVAL, "index = %zu is not below ntt_size = %zu", index, pl->n);
+    if (batch == 0) return CNTT_OK;
+    if (!lwe_out) return fail(CNTT_EINVAL, "lwe_out is NULL");
+    if (!glwe) return fail(CNTT_EINVAL, "glwe is NULL");
+    const size_t w = (size_t)pl->info.word, ob = batch * (glwe_dim * pl->n + 1) * w, gb = batch * (glwe_dim + 1) * pl->n * w;
+    if (ranges_overlap(lwe_out, ob, glwe, gb)) return fail(CNTT_EINVAL, "lwe_out overlaps glwe");
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) return native_extract_device(pl, lwe_out, glwe, glwe_dim, index, batch, st);
+    DevBuf dout, dg;
+    if (int rc = dout.alloc(ob)) return rc;
+    if (int rc = dg.alloc(gb)) return rc;
+    HIP_TRY(hipMemcpyAsync(dg.p, glwe, gb, hipMemcpyHostToDevice, st));
+    if (int rc = native_extract_device(pl, dout.p, dg.p, glwe_dim, index, batch, st)) return rc;
+    HIP_TRY(hipMemcpyAsync(lwe_out, dout.p, ob, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CNTT_OK;
+}
+
+// the argument checks blind_rotate and bootstrap share, up to the NULL key planes; `need` = what the workspace must hold
+static int pbs_check(const cntt_native *pl, const void *const *bsk, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels,
+                     size_t batch, const void *workspace, size_t workspace_bytes, size_t need) {
+    const uint32_t some_rot = 0;
+    if (int rc = gadget_check(pl, base_log, levels, CNTT_SRC_CMUX, &some_rot)) return rc;
+    if (glwe_dim + 1 >= ((size_t)1 << 32)) return fail(CNTT_EINVAL, "glwe_dim too large");
+    const size_t nterms = (glwe_dim + 1) * levels;
+    if (nterms > pl->max_terms)
+        return fail(CNTT_EINVAL, "(glwe_dim + 1) * levels = %zu exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range",
+                    nterms, pl->max_terms);
+    if (batch == 0) return CNTT_OK;
+    if (lwe_dim) {
+        if (!bsk) return fail(CNTT_EINVAL, "bsk_ntt is NULL");
+        for (int i = 0; i < pl->info.nprimes; ++i)
+            if (!bsk[i]) return fail(CNTT_EINVAL, "NULL key residue plane (bsk_ntt[%d])", i);
+    }
+    if (workspace) {
+        if ((uintptr_t)workspace % 16) return fail(CNTT_EINVAL, "workspace is not 16-byte aligned");
+        if (workspace_bytes < need) return fail(CNTT_EINVAL, "workspace_bytes = %zu is below the %zu bytes this call needs", workspace_bytes, need);
+    }
+    return CNTT_OK;
+}
+// host path: copies the key planes to the device
+static int pbs_key_to_device(const cntt_native *pl, const void *const *bsk, size_t bytes, std::vector<DevBuf> &dk, const void **dkey,
+                             hipStream_t st) {
+    for (int i = 0; i < pl->info.nprimes; ++i) {
+        if (int rc = dk[(size_t)i].alloc(bytes)) return rc;
+        dkey[i] = dk[(size_t)i].p;
+        if (bytes) HIP_TRY(hipMemcpyAsync(dk[(size_t)i].p, bsk[i], bytes, hipMemcpyHostToDevice, st));
+    }
+    return CNTT_OK;
+}
+
+extern "C" int cntt_native_blind_rotate_batch(const cntt_native_t *pl, void *acc, const void *lut, int lut_per_element, const uint32_t *rot_t,
+                                              const void *const *bsk_ntt, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels,
+                                              size_t batch, void *workspace, size_t workspace_bytes, cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (batch && !rot_t) return fail(CNTT_EINVAL, "rot_t is NULL");
+    const PbsSizes Z = pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch);
+    if (int rc = pbs_check(pl, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, Z.digits)) return rc;
+    if (batch == 0) return CNTT_OK;
+    if (!acc) return fail(CNTT_EINVAL, "acc is NULL");
+    if (!lut) return fail(CNTT_EINVAL, "lut is NULL");
+    const size_t lb = lut_per_element ? Z.acc : Z.acc / batch;
+    if (ranges_overlap(acc, Z.acc, lut, lb)) return fail(CNTT_EINVAL, "acc overlaps lut");
+    if (ranges_overlap(acc, Z.acc, rot_t, Z.rot)) return fail(CNTT_EINVAL, "acc overlaps rot_t");
+    if (workspace && ranges_overlap(acc, Z.acc, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "acc overlaps workspace");
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) {
+        void *digits = workspace;
+        if (!digits && lwe_dim) HIP_TRY(hipMallocAsync(&digits, Z.digits, st));   // one allocation for the whole loop
+        const int rc = native_blind_rotate_device(pl, acc, lut, lut_per_element != 0, rot_t, bsk_ntt, lwe_dim, glwe_dim, base_log, levels,
+                                                  batch, digits, st);
+        if (!workspace && digits) (void)hipFreeAsync(digits, st);
+        return rc;
+    }
+    for (size_t i = 0; i < (lwe_dim + 1) * batch; ++i)   // host path: the exponents are in reach
+        if ((size_t)rot_t[i] >= 2 * pl->n) return fail(CNTT_EINVAL, "rot_t[%zu] = %u is not below 2n = %zu", i, rot_t[i], 2 * pl->n);
+    const size_t kb = lwe_dim * (glwe_dim + 1) * levels * (glwe_dim + 1) * pl->n * pl->rbytes();
+    DevBuf dacc, dlut, drot, ddig;
+    std::vector<DevBuf> dk((size_t)pl->info.nprimes);
+    const void *dkey[10];
+    if (int rc = dacc.alloc(Z.acc)) return rc;
+    if (int rc = dlut.alloc(lb)) return rc;
+    if (int rc = drot.alloc(Z.rot)) return rc;
+    if (int rc = ddig.alloc(Z.digits)) return rc;
+    if (lwe_dim)
+        if (int rc = pbs_key_to_device(pl, bsk_ntt, kb, dk, dkey, st)) return rc;
+    HIP_TRY(hipMemcpyAsync(dlut.p, lut, lb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(drot.p, rot_t, Z.rot, hipMemcpyHostToDevice, st));
+    if (int rc = native_blind_rotate_device(pl, dacc.p, dlut.p, lut_per_element != 0, (const uint32_t *)drot.p, dkey, lwe_dim, glwe_dim,
+                                            base_log, levels, batch, ddig.p, st))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(acc, dacc.p, Z.acc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CNTT_OK;
+}
+
+// modulus switch -> blind rotation -> extraction of coefficient 0 on device buffers; ws holds digits | rot_t | acc (PbsSizes)
+static int native_bootstrap_device(const cntt_native *pl, void *lwe_out, const void *lwe_in, const void *lut, bool lut_per_element,
+                                   const void *const *bsk, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels, size_t batch,
+                                   const PbsSizes &Z, char *ws, hipStream_t st) {
+    uint32_t *rot_t = reinterpret_cast<uint32_t *>(ws + up256(Z.digits));
+    void *acc = ws + up256(Z.digits) + up256(Z.rot);
+    if (int rc = native_modswitch_device(pl, rot_t, lwe_in, lwe_dim, batch, st)) return rc;
+    if (int rc = native_blind_rotate_device(pl, acc, lut, lut_per_element, rot_t, bsk, lwe_dim, glwe_dim, base_log, levels, batch, ws, st))
+        return rc;
+    return native_extract_device(pl, lwe_out, acc, glwe_dim, 0, batch, st);
+}
+
+extern "C" int cntt_native_bootstrap_batch(const cntt_native_t *pl, void *lwe_out, const void *lwe_in, const void *lut, int lut_per_element,
+                                           const void *const *bsk_ntt, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels,
+                                           size_t batch, void *workspace, size_t workspace_bytes, cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    const PbsSizes Z = pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch);
+    if (int rc = pbs_check(pl, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, Z.total())) return rc;
+    if (batch == 0) return CNTT_OK;
+    if (!lwe_out) return fail(CNTT_EINVAL, "lwe_out is NULL");
+    if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
+    if (!lut) return fail(CNTT_EINVAL, "lut is NULL");
+    const size_t w = (size_t)pl->info.word, ob = batch * (glwe_dim * pl->n + 1) * w, ib = batch * (lwe_dim + 1) * w;
+    const size_t lb = lut_per_element ? Z.acc : Z.acc / batch;
+    if (ranges_overlap(lwe_out, ob, lwe_in, ib)) return fail(CNTT_EINVAL, "lwe_out overlaps lwe_in");
+    if (ranges_overlap(lwe_out, ob, lut, lb)) return fail(CNTT_EINVAL, "lwe_out overlaps lut");
+    if (workspace) {
+        if (ranges_overlap(lwe_out, ob, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_out overlaps workspace");
+        if (ranges_overlap(lwe_in, ib, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_in overlaps workspace");
+        if (ranges_overlap(lut, lb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lut overlaps workspace");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) {
+        void *ws = workspace;
+        if (!ws) HIP_TRY(hipMallocAsync(&ws, Z.total(), st));   // one allocation for the whole call
+        const int rc = native_bootstrap_device(pl, lwe_out, lwe_in, lut, lut_per_element != 0, bsk_ntt, lwe_dim, glwe_dim, base_log, levels,
+                                               batch, Z, static_cast<char *>(ws), st);
+        if (!workspace) (void)hipFreeAsync(ws, st);
+        return rc;
+    }
+    const size_t kb = lwe_dim * (glwe_dim + 1) * levels * (glwe_dim + 1) * pl->n * pl->rbytes();
+    DevBuf dout, din, dlut, dws;
+    std::vector<DevBuf> dk((size_t)pl->info.nprimes);
+    const void *dkey[10];
+    if (int rc = dout.alloc(ob)) return rc;
+    if (int rc = din.alloc(ib)) return rc;
+    if (int rc = dlut.alloc(lb)) return rc;
+    if (int rc = dws.alloc(Z.total())) return rc;
+    if (lwe_dim)
+        if (int rc = pbs_key_to_device(pl, bsk_ntt, kb, dk, dkey, st)) return rc;
+    HIP_TRY(hipMemcpyAsync(din.p, lwe_in, ib, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dlut.p, lut, lb, hipMemcpyHostToDevice, st));
+    if (int rc = native_bootstrap_device(pl, dout.p, din.p, dlut.p, lut_per_element != 0, dkey, lwe_dim, glwe_dim, base_log, levels, batch, Z,
+                                         static_cast<char *>(dws.p), st))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(lwe_out, dout.p, ob, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return CNTT_OK;
 }

@@ -212,6 +212,30 @@ template <cntt_native_kind_t KIND, class R, int NPRIMES, int WORD_BYTES> class N
         check(cntt_native_external_product_decomposed_batch(h_, out, polys, rot, addend, key_ntt, npolys, base_log, levels, mode, nout,
                                                             batch, where, stream));
     }
+    // programmable bootstrap (cntt_pbs.h): modulus switch, blind rotation in place, sample extraction, and all three in one call
+    size_t pbs_workspace_bytes(size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) const {
+        return cntt_native_pbs_workspace_bytes(h_, lwe_dim, glwe_dim, levels, batch);
+    }
+    void lwe_modswitch_batch(uint32_t *rot_t, const void *lwe, size_t lwe_dim, size_t batch, cntt_mem_t where = CNTT_MEM_DEVICE,
+                             void *stream = nullptr) const {
+        check(cntt_native_lwe_modswitch_batch(h_, rot_t, lwe, lwe_dim, batch, where, stream));
+    }
+    void blind_rotate_batch(void *acc, const void *lut, bool lut_per_element, const uint32_t *rot_t, const void *const *bsk_ntt,
+                            size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels, size_t batch, void *workspace = nullptr,
+                            size_t workspace_bytes = 0, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(cntt_native_blind_rotate_batch(h_, acc, lut, lut_per_element ? 1 : 0, rot_t, bsk_ntt, lwe_dim, glwe_dim, base_log, levels,
+                                             batch, workspace, workspace_bytes, where, stream));
+    }
+    void sample_extract_batch(void *lwe_out, const void *glwe, size_t glwe_dim, size_t index, size_t batch,
+                              cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(cntt_native_sample_extract_batch(h_, lwe_out, glwe, glwe_dim, index, batch, where, stream));
+    }
+    void bootstrap_batch(void *lwe_out, const void *lwe_in, const void *lut, bool lut_per_element, const void *const *bsk_ntt,
+                         size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels, size_t batch, void *workspace = nullptr,
+                         size_t workspace_bytes = 0, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(cntt_native_bootstrap_batch(h_, lwe_out, lwe_in, lut, lut_per_element ? 1 : 0, bsk_ntt, lwe_dim, glwe_dim, base_log, levels,
+                                          batch, workspace, workspace_bytes, where, stream));
+    }
 };
 }  // namespace detail
 

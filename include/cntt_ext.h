@@ -55,4 +55,8 @@ size_t cntt_native_max_terms(const cntt_native_t *plan);
  * which carries their semantics. */
 #include "cntt_gadget.h"
 
+/* The programmable bootstrap built on them -- LWE modulus switch, blind rotation in place, sample extraction, and all of it in one
+ * call -- is declared the same way, through a file of its own that carries the conventions. */
+#include "cntt_pbs.h"
+
 #endif /* CNTT_EXT_H */
