@@ -13,9 +13,9 @@ namespace cntt {
 // ---------------------------------------------------------------------------------------------
 enum : int { PW_MUL_NORMALIZE = 0, PW_NORMALIZE = 1, PW_MUL_ACCUMULATE = 2, PW_ADD = 3 };
 
-// STREAM: the operands are larger than STREAM_BYTES (host.hip, 384 MiB) and pass through once -- non-temporal loads and stores (round 5:
+// STREAM: the operands are larger than STREAM_BYTES (host_common.hpp, 384 MiB) and pass through once -- non-temporal loads and stores (round 5:
 // -5 % on 512 MiB operands).  Operands that fit the cache keep the default policy: with the hint a 128 MiB batch that the previous kernel
-// left in the cache is fetched from HBM again (+12 ... +17 %, profiles/r05_small_batch_ab.txt).  The launcher decides (host.hip).
+// left in the cache is fetched from HBM again (+12 ... +17 %, profiles/r05_small_batch_ab.txt).  The launcher decides (host_prime.hip).
 template <class T, int OP, bool STREAM = false>
 __global__ __launch_bounds__(256) void pointwise_kernel(T *__restrict__ a, const T *__restrict__ b,
                                                         const T *__restrict__ c, const ModParams<T> P, size_t count) {
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) void crt_kernel(W *__restrict__ value, CrtArgs
                 const uint32_t d = rr - acc + m;  // in (0, 2m)
                 v[g] = shoup_mulmod32(d, (uint32_t)A.inv[g], A.inv_shoup32[g], m);
             } else {
-                // The digit moduli of every reference plan ascend (host.hip build_crt_args checks it), so each digit
+                // The digit moduli of every reference plan ascend (host_native.hip build_crt_args checks it), so each digit
                 // v[h] < M[h] < M[g] and the group residue rg[g] < M[g] are canonical modulo M[g] as they are.  (A guarded
                 // 64-bit `%` here expands to a long-division routine even though it never runs.)
                 const uint64_t m = A.M[g];

@@ -1,0 +1,260 @@
+// What the host units of libcntt_hip.so share (host_core / host_prime / host_native / host_native_ext / host_product .hip): the plan
+// structs behind the C ABI, error reporting, the host-slice staging and the functions that cross unit borders.  Internal, never
+// installed.  Every __global__ template is launched -- and so instantiated -- by exactly ONE unit; the others call the host function
+// that owns the launch, declared here and explicitly instantiated there.  Nothing declared here is exported.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/cntt.h"
+#include "../../include/cntt_ext.h"
+#include "host_math.hpp"
+#include "native_ext.hpp"
+#include "ntt_launch.hpp"
+
+using namespace cntt;
+using host::u128;
+
+#pragma GCC visibility push(hidden)
+// ---------------------------------------------------------------------------------------------
+// errors (host_core.hip: the thread-local message behind cntt_last_error)
+// ---------------------------------------------------------------------------------------------
+int fail(int code, const char *fmt, ...);
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return fail(CNTT_EDEVICE, "%s: %s", #expr, hipGetErrorString(e_));    \
+    } while (0)
+
+// Grid of the element-wise kernels (grid-stride loops: any grid is correct): one 256-thread block per 256 work items, NOT capped at
+// a few blocks per CU.  Measured (tools/pw_probe.py, 65536 x 1024 u64): mul_assign_normalize 0.374 -> 0.271 ms (4.3 -> 5.9 TB/s),
+// normalize 0.232 -> 0.178 ms (4.6 -> 6.0 TB/s) against the 2048-block persistent form; split / CRT / Garner kernels -4 ... -7 %.
+// The cap: a dispatch holds at most 2^32 - 1 work-items per dimension (grid_size_x of the AQL packet is a uint32), i.e. fewer than
+// 2^24 blocks of 256 threads; beyond it (16 GiB of u32 and up -- plausible on 288 GB) the kernels' 64-bit grid-stride loops
+// take over.  Exported as cntt_ew_grid (host_core.hip).
+inline unsigned ew_grid(size_t work_items) {
+    const size_t blocks = (work_items + 255) / 256;
+    return (unsigned)std::max<size_t>(1, std::min<size_t>(blocks, ((size_t)1 << 24) - 1));
+}
+
+// Working set (bytes one call reads and writes) above which the stand-alone transforms and the pointwise kernels take the
+// non-temporal policy.  384 MiB is 1.5 x the 256 MiB Infinity Cache: batches that fit the cache lost 3-17 % with the hint.
+// tests/test_gpu_multitrip_transforms.py (STREAM_BYTES) restates this number for the streaming tests.
+constexpr size_t STREAM_BYTES = (size_t)384 << 20;
+
+// The host-slice path (CNTT_MEM_HOST) of every call: device copies of the caller's buffers.  in / inout enqueue their host-to-device
+// copy on the stream when they are called; out / inout record a copy back, which finish() enqueues in the order of the calls before
+// the one synchronise.  After a failed allocation or copy every later call returns nullptr and status() / finish() give the code.
+// The device path (CNTT_MEM_DEVICE) never builds one: it allocates nothing here and never synchronises.
+class Staging {
+    struct Back {
+        void *host, *dev;
+        size_t bytes;
+    };
+    hipStream_t st_;
+    int rc_ = CNTT_OK;
+    std::vector<void *> dev_;
+    std::vector<Back> back_;
+
+  public:
+    explicit Staging(hipStream_t st) : st_(st) {}
+    Staging(const Staging &) = delete;
+    ~Staging() {
+        for (void *p : dev_) (void)hipFree(p);
+    }
+    int status() const { return rc_; }
+    void *alloc(size_t bytes) {   // device scratch that lives as long as this object
+        void *p = nullptr;
+        if (rc_ != CNTT_OK) return nullptr;
+        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) {
+            rc_ = fail(CNTT_EDEVICE, "hipMalloc(%zu) failed (no GPU, or out of device memory)", bytes);
+            return nullptr;
+        }
+        dev_.push_back(p);
+        return p;
+    }
+    void *in(const void *host, size_t bytes) {
+        void *p = alloc(bytes);
+        const hipError_t e = p && bytes ? hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, st_) : hipSuccess;
+        if (e != hipSuccess) rc_ = fail(CNTT_EDEVICE, "hipMemcpyAsync(host to device, %zu bytes): %s", bytes, hipGetErrorString(e));
+        return rc_ == CNTT_OK ? p : nullptr;
+    }
+    void *out(void *host, size_t bytes) {
+        void *p = alloc(bytes);
+        if (p && bytes) back_.push_back({host, p, bytes});
+        return p;
+    }
+    void *inout(void *host, size_t bytes) {
+        void *p = in(host, bytes);
+        if (p && bytes) back_.push_back({host, p, bytes});
+        return p;
+    }
+    int finish() {
+        if (rc_ != CNTT_OK) return rc_;
+        for (const Back &b : back_) HIP_TRY(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, st_));
+        HIP_TRY(hipStreamSynchronize(st_));
+        return CNTT_OK;
+    }
+};
+
+#pragma GCC visibility pop
+
+// ---------------------------------------------------------------------------------------------
+// the plans behind the opaque handles of include/cntt.h: prime (host_prime.hip) ...
+// ---------------------------------------------------------------------------------------------
+template <class T> struct DeviceTables {
+    TwPair<T> *fwd = nullptr, *inv = nullptr;
+    // plans whose LDS-resident transforms run in a 64-bit-only class: the same twiddles in that class's form --
+    // CLS_FP / CLS_FP51: (c, c / p) doubles, c centred in (-p/2, p/2];  CLS_PM64: plain residues;  CLS_FPW: c as one double
+    TwPair<T> *fwd_fp = nullptr, *inv_fp = nullptr;
+};
+template <class T> struct DeviceCache;   // per-device replicas of the tables (host_prime.hip)
+
+template <class T> struct PrimePlan {
+    static constexpr int B = sizeof(T) * 8;
+    size_t n = 0;
+    int logn = 0;
+    T p = 0;
+    uint64_t root = 0;
+    bool has_shoup = false;
+    // reference-layout tables (src/prime64.rs:221-236)
+    std::vector<T> twid, twid_shoup, inv_twid, inv_twid_shoup;
+    T p_barrett = 0, n_inv = 0, n_inv_shoup = 0;
+    uint32_t big_q = 0;
+    ModParams<T> mp{};
+    std::shared_ptr<DeviceCache<T>> cache;
+};
+
+struct cntt_plan64 : PrimePlan<uint64_t> {};
+struct cntt_plan32 : PrimePlan<uint32_t> {};
+
+// ---------------------------------------------------------------------------------------------
+// ... native (host_native.hip; external product, gadget decomposition and bootstrap: host_native_ext.hip) ...
+// ---------------------------------------------------------------------------------------------
+// src/lib.rs:453-462 and :601-606
+constexpr uint32_t PRIMES32[10] = {1062862849u, 1063059457u, 1064697857u, 1065484289u, 1068236801u,
+                                   1068433409u, 1068564481u, 1069219841u, 1071513601u, 1073479681u};
+constexpr uint64_t PRIMES52[6] = {1125899881086977ull, 1125899885412353ull, 1125899886395393ull,
+                                  1125899899174913ull, 1125899902124033ull, 1125899903107073ull};
+
+struct NativeKindInfo {
+    int nprimes, word, is52, binary, ngroups;
+    int ga[5], gb[5];  // prime indices of each mixed-radix group (gb = -1: single prime)
+};
+struct NativeCache;   // the workspace of the composed pipeline, per device (host_native.hip)
+
+struct cntt_native {
+    cntt_native_kind_t kind;
+    NativeKindInfo info;
+    size_t n = 0;
+    std::vector<std::unique_ptr<cntt_plan32>> p32;
+    std::vector<std::unique_ptr<cntt_plan64>> p64;
+    CrtArgs crt{};
+    // accumulating CRT of the whole-product kernel (native_fused.hpp, native_product_acc): constants, and the per-prime
+    // parameters whose last-inverse-stage constants carry (M / P_i)^-1 / n
+    AccArgs acc{};
+    ModParams<uint32_t> mp_acc[10];
+    bool has_acc = false;
+    // Plan52 kinds (round 5): negacyclic_polymul returns the wrapping image of the EXACT integer product, which does not depend on the
+    // primes it was computed with (native_fused.hpp, accumulating CRT) -- so it runs the whole-product kernel of the Plan32 kind with the
+    // same words (30-bit primes: the faster arithmetic on this chip; the reference offers Plan52 for AVX-512 IFMA hosts).  fwd / inv of
+    // the plan, whose 50-bit residues are visible, stay on its own primes.  Absent where the Plan32 kind does not exist (n < 32).
+    std::unique_ptr<cntt_native> via32;
+    std::shared_ptr<NativeCache> cache;
+    size_t max_terms = 1;   // cntt_native_max_terms (cntt_ext.h)
+    size_t rbytes() const { return info.is52 ? 8 : 4; }
+    uint64_t prime(int i) const { return info.is52 ? PRIMES52[i] : (uint64_t)PRIMES32[i]; }
+};
+
+// ---------------------------------------------------------------------------------------------
+// ... and product::Plan (host_product.hip)
+// ---------------------------------------------------------------------------------------------
+struct cntt_product {
+    size_t n = 0;
+    uint64_t modulus = 0;
+    std::vector<uint64_t> primes;  // ascending, 1s removed
+    std::vector<std::shared_ptr<cntt_plan32>> p32;
+    std::vector<std::shared_ptr<cntt_plan64>> p64;
+    std::vector<uint64_t> modular_inverses;  // src/product.rs:207-229
+    ProductArgs args{};
+    size_t len32() const { return (n / 2) * p32.size(); }          // ntt_domain_len_u32 src/product.rs:261-263
+    size_t domain_len() const { return len32() + n * p64.size(); } // ntt_domain_len     src/product.rs:268-270
+};
+
+// ---------------------------------------------------------------------------------------------
+// what crosses unit borders: the prime launchers (host_prime.hip) ...
+// ---------------------------------------------------------------------------------------------
+#pragma GCC visibility push(hidden)
+template <class T> inline T shoup_of(T x, T p) { return (T)((((u128)x) << (sizeof(T) * 8)) / p); }
+inline bool alt_tables(int cls) { return is_fp_class(cls) || cls == CLS_PM64 || cls == CLS_FPW; }
+// transform class of the LDS-resident kernels for this plan (the global-stage path of larger sizes is integer-only)
+template <class T> inline int transform_class(const PrimePlan<T> *pl) {
+    if (pl->logn > MaxLdsLogN<T>::value) return (int)pl->mp.cls;
+    if (pl->mp.fp == CLS_FPW && pl->logn > MAX_FPW_LOGN) return (int)pl->mp.cls;
+    if (pl->mp.fp) return (int)pl->mp.fp;
+    if (pl->mp.pm_c) return (int)CLS_PM64;
+    return (int)pl->mp.cls;
+}
+
+// instantiated in host_prime.hip for (uint32_t, cntt_plan32) and (uint64_t, cntt_plan64); all on device pointers
+template <class T, class PlanT> int plan_new(size_t n, T p, PlanT **out);
+template <class T> int device_tables(const PrimePlan<T> *pl, DeviceTables<T> *out);
+template <class T> int ntt_device(const PrimePlan<T> *pl, T *d, size_t batch, bool inv, hipStream_t st);
+template <class T, int OP> int pointwise_device(const PrimePlan<T> *pl, T *a, const T *b, const T *c, size_t count, hipStream_t st);
+template <class T> int mul_ntt_device(const PrimePlan<T> *pl, T *lhs, const T *rhs, size_t batch, hipStream_t st);
+template <class T>
+int external_product_device(const PrimePlan<T> *pl, T *out, const T *terms, const T *key, size_t nterms, size_t nout, size_t batch,
+                            bool accumulate, hipStream_t st);
+
+// ... and the native pieces (host_native.hip)
+SplitArgs native_split_args(const cntt_native *pl, void *const *res);
+int native_split_device(const cntt_native *pl, const void *value, void *const *res, size_t count, bool binary, hipStream_t st);
+int native_crt_device(const cntt_native *pl, void *value, void *const *res, size_t count, hipStream_t st);
+
+// CNTT_OK: enqueued; FUSED_NONE: no fused kernel for this plan / size (the caller composes)
+constexpr int FUSED_NONE = -1;
+// The six Plan32 kinds, the ones with fused kernels: cntt_native_kind_t -> the KIND parameter of NativeShape / launch_native_*, handed
+// to f as a std::integral_constant.  hipErrorNotSupported for the Plan52 kinds.
+template <class F> hipError_t with_plan32_kind(cntt_native_kind_t kind, F &&f) {
+    switch (kind) {
+    case CNTT_NATIVE32_PLAN32: return f(std::integral_constant<int, 0>{});
+    case CNTT_NATIVE64_PLAN32: return f(std::integral_constant<int, 1>{});
+    case CNTT_NATIVE128_PLAN32: return f(std::integral_constant<int, 2>{});
+    case CNTT_NATIVE_BINARY32_PLAN32: return f(std::integral_constant<int, 3>{});
+    case CNTT_NATIVE_BINARY64_PLAN32: return f(std::integral_constant<int, 4>{});
+    case CNTT_NATIVE_BINARY128_PLAN32: return f(std::integral_constant<int, 5>{});
+    default: return hipErrorNotSupported;
+    }
+}
+// launch(kind, rc) enqueues the fused kernel `what` of the plan's kind: a CNTT_ code it stores in rc wins; its hipErrorNotSupported
+// means FUSED_NONE
+template <class F> int native_fused_launch(const cntt_native *pl, const char *what, F &&launch) {
+    int rc = CNTT_OK;
+    const hipError_t e = with_plan32_kind(pl->kind, [&](auto kind) { return launch(kind, rc); });
+    if (rc != CNTT_OK) return rc;
+    if (e == hipSuccess) return CNTT_OK;
+    if (e != hipErrorNotSupported) return fail(CNTT_EDEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
+    (void)hipGetLastError();
+    return FUSED_NONE;
+}
+// tables of the accumulating-CRT kernels: the primes' twiddles with the parameters of build_acc_args and, with `key`, its planes
+template <int KIND>
+int native_acc_tables(const cntt_native *pl, const void *const *key, FusedTables<NativeShape<KIND>::KP> *Facc, KeyPlanes *K) {
+    for (int i = 0; i < NativeShape<KIND>::KP; ++i) {
+        DeviceTables<uint32_t> t;
+        if (int rc = device_tables(pl->p32[(size_t)i].get(), &t)) return rc;
+        Facc->twf[i] = t.fwd;
+        Facc->twi[i] = t.inv;
+        Facc->P[i] = pl->mp_acc[i];
+        if (key) K->k[i] = static_cast<const uint32_t *>(key[i]);
+    }
+    return CNTT_OK;
+}
+#pragma GCC visibility pop

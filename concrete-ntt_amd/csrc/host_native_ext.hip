@@ -1,0 +1,519 @@
+// libcntt_hip.so host side, what is built on the native plans without a counterpart in the reference: the external product
+// (include/cntt_ext.h), rotation / gadget decomposition and the external product on undecomposed polynomials (include/cntt_gadget.h),
+// the programmable bootstrap (include/cntt_pbs.h).
+#include <cstdio>
+
+#include "host_common.hpp"
+#include "native_gadget.hpp"
+#include "native_pbs.hpp"
+
+// ---------------------------------------------------------------------------------------------
+// external product of the native plans (include/cntt_ext.h; no counterpart in the reference)
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t cntt_native_max_terms(const cntt_native_t *pl) { return pl ? pl->max_terms : 0; }
+
+// fused kernel (native_ext.hpp) for the Plan32 kinds at 32 <= n <= 4096; FUSED_NONE where it does not exist
+static int native_ext_fused(const cntt_native *pl, void *out, const void *terms, const void *const *key, size_t nterms, size_t nout,
+                            size_t batch, bool accumulate, hipStream_t st) {
+    if (pl->info.is52 || !pl->has_acc || debug_switch(DBG_NATIVE_EXT) == 0 || batch >= ((size_t)1 << 32) ||
+        nterms >= ((size_t)1 << 32) || nout >= ((size_t)1 << 32))
+        return FUSED_NONE;
+    return native_fused_launch(pl, "fused external product", [&](auto kind, int &rc) {
+        constexpr int KIND = decltype(kind)::value;
+        FusedTables<NativeShape<KIND>::KP> Facc{};
+        KeyPlanes K{};
+        if ((rc = native_acc_tables<KIND>(pl, key, &Facc, &K))) return hipErrorUnknown;
+        const SplitArgs S = native_split_args(pl, nullptr);
+        return launch_native_ext<KIND>(pl->p32[0]->logn, out, terms, K, &Facc, S, pl->acc, (uint32_t)batch, (uint32_t)nterms, (uint32_t)nout,
+                                       accumulate, st);
+    });
+}
+
+// word width of a native kind -> its word type, handed to f as a value
+template <class F> static auto with_word(const cntt_native *pl, F &&f) {
+    switch (pl->info.word) {
+    case 4: return f(uint32_t{});
+    case 8: return f(uint64_t{});
+    default: return f(Word128{});
+    }
+}
+// a[i] += b[i] modulo 2^w
+static int word_add_launch(const cntt_native *pl, void *a, const void *b, size_t count, hipStream_t st) {
+    with_word(pl, [&](auto w) {
+        using W = decltype(w);
+        hipLaunchKernelGGL((native_word_add_kernel<W>), dim3(ew_grid(count)), dim3(256), 0, st, (W *)a, (const W *)b, count);
+    });
+    if (hipGetLastError() != hipSuccess) return fail(CNTT_EDEVICE, "native_word_add_kernel launch failed");
+    return CNTT_OK;
+}
+
+// composed: residue split of all terms, one mul_accumulate chain per prime on the plane layout (its unnormalised inverse carries a
+// factor n: a normalize pass takes it off), one CRT -- into `out`, or into scratch and then added to `out` modulo 2^w
+static int native_ext_composed(const cntt_native *pl, void *out, const void *terms, const void *const *key, size_t nterms, size_t nout,
+                               size_t batch, bool accumulate, hipStream_t st) {
+    const int k = pl->info.nprimes;
+    const size_t n = pl->n, rb = pl->rbytes(), tcount = batch * nterms * n, ocount = batch * nout * n;
+    const size_t wbytes = (size_t)pl->info.word;
+    const size_t bytes = (size_t)k * (tcount + ocount) * rb + (accumulate ? ocount * wbytes : 0);
+    char *scratch = nullptr;
+    HIP_TRY(hipMallocAsync((void **)&scratch, bytes, st));
+    void *T[10], *O[10];
+    for (int i = 0; i < k; ++i) {
+        T[i] = scratch + (size_t)i * tcount * rb;
+        O[i] = scratch + ((size_t)k * tcount + (size_t)i * ocount) * rb;
+    }
+    void *crt_out = accumulate ? scratch + (size_t)k * (tcount + ocount) * rb : out;
+    int rc = native_split_device(pl, terms, T, tcount, false, st);
+    for (int i = 0; i < k && rc == CNTT_OK; ++i) {
+        if (pl->info.is52) {
+            const cntt_plan64 *sub = pl->p64[(size_t)i].get();
+            rc = external_product_device<uint64_t>(sub, (uint64_t *)O[i], (const uint64_t *)T[i], (const uint64_t *)key[i], nterms, nout,
+                                                   batch, false, st);
+            if (rc == CNTT_OK) rc = pointwise_device<uint64_t, PW_NORMALIZE>(sub, (uint64_t *)O[i], nullptr, nullptr, ocount, st);
+        } else {
+            const cntt_plan32 *sub = pl->p32[(size_t)i].get();
+            rc = external_product_device<uint32_t>(sub, (uint32_t *)O[i], (const uint32_t *)T[i], (const uint32_t *)key[i], nterms, nout,
+                                                   batch, false, st);
+            if (rc == CNTT_OK) rc = pointwise_device<uint32_t, PW_NORMALIZE>(sub, (uint32_t *)O[i], nullptr, nullptr, ocount, st);
+        }
+    }
+    if (rc == CNTT_OK) rc = native_crt_device(pl, crt_out, O, ocount, st);
+    if (rc == CNTT_OK && accumulate) rc = word_add_launch(pl, out, crt_out, ocount, st);
+    (void)hipFreeAsync(scratch, st);
+    return rc;
+}
+
+static int native_ext_device(const cntt_native *pl, void *out, const void *terms, const void *const *key, size_t nterms, size_t nout,
+                             size_t batch, bool accumulate, hipStream_t st) {
+    if (nterms == 0) {   // the empty sum
+        if (!accumulate) HIP_TRY(hipMemsetAsync(out, 0, batch * nout * pl->n * (size_t)pl->info.word, st));
+        return CNTT_OK;
+    }
+    const int rc = native_ext_fused(pl, out, terms, key, nterms, nout, batch, accumulate, st);
+    if (rc != FUSED_NONE) return rc;
+    return native_ext_composed(pl, out, terms, key, nterms, nout, batch, accumulate, st);
+}
+
+// key residue planes, one per prime: none may be NULL (`name`: the argument as the message names it, or nullptr)
+static int check_key_planes(const cntt_native *pl, const void *const *key, const char *name) {
+    for (int i = 0; i < pl->info.nprimes; ++i) {
+        if (key[i]) continue;
+        char where[48] = "";
+        if (name) snprintf(where, sizeof where, " (%s[%d])", name, i);
+        return fail(CNTT_EINVAL, "NULL key residue plane%s", where);
+    }
+    return CNTT_OK;
+}
+// host path: their device copies, `bytes` each (no bytes: `key` itself may be NULL)
+static void key_planes_to_device(const cntt_native *pl, Staging &s, const void *const *key, size_t bytes, const void **dkey) {
+    for (int i = 0; i < pl->info.nprimes; ++i) dkey[i] = s.in(bytes ? key[i] : nullptr, bytes);
+}
+
+extern "C" int cntt_native_external_product_batch(const cntt_native_t *pl, void *out, const void *terms, const void *const *key_ntt,
+                                                  size_t nterms, size_t nout, size_t batch, int accumulate, cntt_mem_t where,
+                                                  void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (nterms > pl->max_terms)
+        return fail(CNTT_EINVAL, "nterms = %zu exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range", nterms,
+                    pl->max_terms);
+    if (batch == 0 || nout == 0) return CNTT_OK;
+    if (!out) return fail(CNTT_EINVAL, "NULL argument");
+    if (nterms) {
+        if (!terms || !key_ntt) return fail(CNTT_EINVAL, "NULL argument");
+        if (int rc = check_key_planes(pl, key_ntt, nullptr)) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) return native_ext_device(pl, out, terms, key_ntt, nterms, nout, batch, accumulate != 0, st);
+    const size_t n = pl->n, w = (size_t)pl->info.word, ob = batch * nout * n * w, tb = batch * nterms * n * w;
+    Staging s(st);
+    const void *dkey[10];
+    key_planes_to_device(pl, s, key_ntt, nterms * nout * n * pl->rbytes(), dkey);
+    void *dout = accumulate ? s.inout(out, ob) : s.out(out, ob);
+    const void *dt = s.in(terms, tb);
+    if (int rc = s.status()) return rc;
+    if (int rc = native_ext_device(pl, dout, dt, dkey, nterms, nout, batch, accumulate != 0, st)) return rc;
+    return s.finish();
+}
+
+// ---------------------------------------------------------------------------------------------
+// rotation / CMux difference / signed gadget decomposition and the external product on undecomposed polynomials
+// (include/cntt_gadget.h, native_gadget.hpp)
+// ---------------------------------------------------------------------------------------------
+static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return abytes && bbytes && x < y + bbytes && y < x + abytes;
+}
+// the checks the two calls share; wbits = word width of the kind
+static int gadget_check(const cntt_native *pl, unsigned base_log, unsigned levels, int mode, const uint32_t *rot) {
+    const unsigned wbits = 8u * (unsigned)pl->info.word;
+    if (base_log == 0) return fail(CNTT_EINVAL, "base_log is 0");
+    if (levels == 0) return fail(CNTT_EINVAL, "levels is 0");
+    if ((uint64_t)base_log * levels > wbits) return fail(CNTT_EINVAL, "base_log * levels = %u * %u exceeds the word width %u", base_log, levels, wbits);
+    if (mode != CNTT_SRC_PLAIN && mode != CNTT_SRC_ROTATE && mode != CNTT_SRC_CMUX) return fail(CNTT_EINVAL, "src_mode %d is not a cntt_src_mode_t", mode);
+    if (mode != CNTT_SRC_PLAIN && !rot) return fail(CNTT_EINVAL, "rot is NULL and src_mode reads it");
+    return CNTT_OK;
+}
+// off = 2^(s-1) + K 2^s mod 2^w, K = sum_l (B/2) B^(levels-l), s = w - base_log levels (native_gadget.hpp)
+static u128 gadget_offset(unsigned wbits, unsigned base_log, unsigned levels) {
+    const unsigned s = wbits - base_log * levels;
+    u128 off = s ? (u128)1 << (s - 1) : 0;
+    for (unsigned l = 1; l <= levels; ++l) off += (u128)1 << (wbits - base_log * l + base_log - 1);   // (B/2) B^(levels-l) 2^s
+    return off;   // (wbits < 128: the caller truncates)
+}
+template <class W> static W word_from(u128 v) { return (W)v; }
+template <> Word128 word_from<Word128>(u128 v) { return Word128{(uint64_t)v, (uint64_t)(v >> 64)}; }
+
+template <class W>
+static int gadget_launch_w(void *terms, const void *polys, const uint32_t *rot, size_t npolys, unsigned base_log, unsigned levels, int mode,
+                           size_t batch, int logn, hipStream_t st) {
+    constexpr unsigned WB = sizeof(W) * 8;
+    GadgetConst<W> G{};
+    G.off = word_from<W>(gadget_offset(WB, base_log, levels));
+    G.mask = word_from<W>(base_log == 128 ? ~(u128)0 : ((u128)1 << base_log) - 1);
+    G.half = word_from<W>((u128)1 << (base_log - 1));
+    G.base_log = base_log;
+    G.levels = levels;
+    G.npolys = (uint32_t)npolys;
+    G.rotated = mode != CNTT_SRC_PLAIN;
+    G.cmux = mode == CNTT_SRC_CMUX;
+    const size_t total = batch * npolys, n = (size_t)1 << logn;
+    const unsigned grid = ew_grid(total * n * sizeof(W) / 16);
+    // the terms against STREAM_BYTES, as the pointwise kernels decide it: larger ones pass through once (non-temporal stores)
+    if (total * levels * n * sizeof(W) > STREAM_BYTES)
+        hipLaunchKernelGGL((native_gadget_kernel<W, true>), dim3(grid), dim3(256), 0, st, (W *)terms, (const W *)polys, rot, G, (uint32_t)logn, total);
+    else
+        hipLaunchKernelGGL((native_gadget_kernel<W, false>), dim3(grid), dim3(256), 0, st, (W *)terms, (const W *)polys, rot, G, (uint32_t)logn, total);
+    if (hipGetLastError() != hipSuccess) return fail(CNTT_EDEVICE, "native_gadget_kernel launch failed");
+    return CNTT_OK;
+}
+static int native_logn(const cntt_native *pl) {
+    int logn = 0;
+    while (((size_t)1 << logn) < pl->n) ++logn;
+    return logn;
+}
+static int native_gadget_device(const cntt_native *pl, void *terms, const void *polys, const uint32_t *rot, size_t npolys, unsigned base_log,
+                                unsigned levels, int mode, size_t batch, hipStream_t st) {
+    if (batch == 0 || npolys == 0) return CNTT_OK;
+    if (npolys >= ((size_t)1 << 32)) return fail(CNTT_EINVAL, "npolys too large");
+    return with_word(pl, [&](auto w) {
+        return gadget_launch_w<decltype(w)>(terms, polys, rot, npolys, base_log, levels, mode, batch, native_logn(pl), st);
+    });
+}
+// host path: the rotation exponents are in reach, so one that is not below 2n is an error there (`name`: the argument in the message)
+static int check_rot_host(const cntt_native *pl, const uint32_t *rot, size_t count, const char *name) {
+    for (size_t i = 0; i < count; ++i)
+        if ((size_t)rot[i] >= 2 * pl->n) return fail(CNTT_EINVAL, "%s[%zu] = %u is not below 2n = %zu", name, i, rot[i], 2 * pl->n);
+    return CNTT_OK;
+}
+
+extern "C" int cntt_native_gadget_decompose_batch(const cntt_native_t *pl, void *terms, const void *polys, const uint32_t *rot,
+                                                  size_t npolys, unsigned base_log, unsigned levels, cntt_src_mode_t src_mode, size_t batch,
+                                                  cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (int rc = gadget_check(pl, base_log, levels, (int)src_mode, rot)) return rc;
+    if (batch == 0 || npolys == 0) return CNTT_OK;
+    if (!terms || !polys) return fail(CNTT_EINVAL, "NULL argument");
+    const size_t pb = batch * npolys * pl->n * (size_t)pl->info.word, tb = pb * levels;
+    if (ranges_overlap(terms, tb, polys, pb)) return fail(CNTT_EINVAL, "terms overlaps polys");
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) return native_gadget_device(pl, terms, polys, rot, npolys, base_log, levels, (int)src_mode, batch, st);
+    const bool rotated = src_mode != CNTT_SRC_PLAIN;
+    if (rotated)
+        if (int rc = check_rot_host(pl, rot, batch, "rot")) return rc;
+    Staging s(st);
+    void *dt = s.out(terms, tb);
+    const void *dp = s.in(polys, pb);
+    const uint32_t *dr = rotated ? (const uint32_t *)s.in(rot, batch * sizeof(uint32_t)) : nullptr;
+    if (int rc = s.status()) return rc;
+    if (int rc = native_gadget_device(pl, dt, dp, dr, npolys, base_log, levels, (int)src_mode, batch, st)) return rc;
+    return s.finish();
+}
+
+// fused kernel (native_gadget.hpp): the 32- and 64-bit Plan32 kinds at 32 <= n <= 4096, base_log <= 31; FUSED_NONE elsewhere
+static int native_ext_gadget_fused(const cntt_native *pl, void *out, const GadgetCall &G, const void *const *key, size_t nout, size_t batch,
+                                   hipStream_t st) {
+    if (pl->info.is52 || !pl->has_acc || pl->info.word > 8 || G.base_log > 31 || debug_switch(DBG_NATIVE_GADGET) <= 0 ||
+        batch >= ((size_t)1 << 32) || nout >= ((size_t)1 << 32))
+        return FUSED_NONE;
+    return native_fused_launch(pl, "fused decomposing external product", [&](auto kind, int &rc) {
+        constexpr int KIND = decltype(kind)::value;
+        if constexpr (sizeof(typename NativeShape<KIND>::W) > 8) {
+            return hipErrorNotSupported;
+        } else {
+            FusedTables<NativeShape<KIND>::KP> Facc{};
+            KeyPlanes K{};
+            if ((rc = native_acc_tables<KIND>(pl, key, &Facc, &K))) return hipErrorUnknown;
+            const SplitArgs S = native_split_args(pl, nullptr);
+            return launch_native_ext_gadget<KIND>(pl->p32[0]->logn, out, G, K, &Facc, S, pl->acc, (uint32_t)batch, (uint32_t)nout, st);
+        }
+    });
+}
+// addend: nullptr, `out`, or a buffer that does not overlap out (checked by the caller)
+static int native_ext_gadget_device(const cntt_native *pl, void *out, const void *polys, const uint32_t *rot, const void *addend,
+                                    const void *const *key, size_t npolys, unsigned base_log, unsigned levels, int mode, size_t nout,
+                                    size_t batch, hipStream_t st) {
+    const size_t n = pl->n, w = (size_t)pl->info.word, ocount = batch * nout * n, nterms = npolys * levels;
+    if (nterms == 0) {   // the empty sum: out = addend, or zero
+        if (!addend) HIP_TRY(hipMemsetAsync(out, 0, ocount * w, st));
+        else if (addend != out) HIP_TRY(hipMemcpyAsync(out, addend, ocount * w, hipMemcpyDeviceToDevice, st));
+        return CNTT_OK;
+    }
+    GadgetCall G{};
+    G.polys = polys;
+    G.rot = mode == CNTT_SRC_PLAIN ? nullptr : rot;
+    G.addend = addend == out ? nullptr : addend;
+    G.off = w <= 8 ? (uint64_t)gadget_offset(8u * (unsigned)w, base_log, levels) : 0;   // (the fused kernel: u32 / u64 words)
+    G.npolys = (uint32_t)npolys;
+    G.levels = levels;
+    G.base_log = base_log;
+    G.cmux = mode == CNTT_SRC_CMUX;
+    G.add_out = addend == out;
+    const int rc = native_ext_gadget_fused(pl, out, G, key, nout, batch, st);
+    if (rc != FUSED_NONE) return rc;
+    // composed: the digits into stream-ordered scratch, the external product on them, then the addend
+    char *scratch = nullptr;
+    HIP_TRY(hipMallocAsync((void **)&scratch, batch * nterms * n * w, st));
+    int rc2 = native_gadget_device(pl, scratch, polys, rot, npolys, base_log, levels, mode, batch, st);
+    if (rc2 == CNTT_OK) rc2 = native_ext_device(pl, out, scratch, key, nterms, nout, batch, addend == out, st);
+    if (rc2 == CNTT_OK && addend && addend != out) rc2 = word_add_launch(pl, out, addend, ocount, st);
+    (void)hipFreeAsync(scratch, st);
+    return rc2;
+}
+
+extern "C" int cntt_native_external_product_decomposed_batch(const cntt_native_t *pl, void *out, const void *polys, const uint32_t *rot,
+                                                             const void *addend, const void *const *key_ntt, size_t npolys,
+                                                             unsigned base_log, unsigned levels, cntt_src_mode_t src_mode, size_t nout,
+                                                             size_t batch, cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (int rc = gadget_check(pl, base_log, levels, (int)src_mode, rot)) return rc;
+    const size_t nterms = npolys * levels;
+    if (nterms > pl->max_terms)
+        return fail(CNTT_EINVAL, "npolys * levels = %zu exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range", nterms,
+                    pl->max_terms);
+    if (batch == 0 || nout == 0) return CNTT_OK;
+    if (!out) return fail(CNTT_EINVAL, "out is NULL");
+    const size_t n = pl->n, w = (size_t)pl->info.word, ob = batch * nout * n * w, pb = batch * npolys * n * w;
+    if (nterms) {
+        if (!polys || !key_ntt) return fail(CNTT_EINVAL, "NULL argument");
+        if (int rc = check_key_planes(pl, key_ntt, nullptr)) return rc;
+        if (ranges_overlap(out, ob, polys, pb)) return fail(CNTT_EINVAL, "out overlaps polys");
+    }
+    if (addend && addend != out && ranges_overlap(out, ob, addend, ob)) return fail(CNTT_EINVAL, "addend overlaps out without being out");
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE)
+        return native_ext_gadget_device(pl, out, polys, rot, addend, key_ntt, npolys, base_log, levels, (int)src_mode, nout, batch, st);
+    const bool rotated = nterms && src_mode != CNTT_SRC_PLAIN;
+    if (rotated)
+        if (int rc = check_rot_host(pl, rot, batch, "rot")) return rc;
+    Staging s(st);
+    const void *dkey[10];
+    key_planes_to_device(pl, s, key_ntt, nterms * nout * n * pl->rbytes(), dkey);
+    const void *dp = s.in(polys, pb);
+    const uint32_t *dr = rotated ? (const uint32_t *)s.in(rot, batch * sizeof(uint32_t)) : nullptr;
+    void *dout = addend == out ? s.inout(out, ob) : s.out(out, ob);
+    const void *dadd = addend == out ? dout : addend && addend == polys && pb == ob ? dp : addend ? s.in(addend, ob) : nullptr;
+    if (int rc = s.status()) return rc;
+    if (int rc = native_ext_gadget_device(pl, dout, dp, dr, dadd, dkey, npolys, base_log, levels, (int)src_mode, nout, batch, st)) return rc;
+    return s.finish();
+}
+
+// ---------------------------------------------------------------------------------------------
+// programmable bootstrap: modulus switch, blind rotation in place, sample extraction (include/cntt_pbs.h, native_pbs.hpp)
+// ---------------------------------------------------------------------------------------------
+static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+// the three parts of the workspace, in bytes and in this order (cntt_pbs.h states the formula)
+struct PbsSizes {
+    size_t digits, rot, acc;
+    size_t total() const { return up256(digits) + up256(rot) + up256(acc); }
+};
+static PbsSizes pbs_sizes(const cntt_native *pl, size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) {
+    const size_t pb = batch * (glwe_dim + 1) * pl->n * (size_t)pl->info.word;
+    return PbsSizes{pb * levels, (lwe_dim + 1) * batch * sizeof(uint32_t), pb};
+}
+extern "C" size_t cntt_native_pbs_workspace_bytes(const cntt_native_t *pl, size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) {
+    return pl ? pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch).total() : 0;
+}
+
+static int native_modswitch_device(const cntt_native *pl, uint32_t *rot_t, const void *lwe, size_t lwe_dim, size_t batch, hipStream_t st) {
+    if (native_logn(pl) > 30) return fail(CNTT_EINVAL, "ntt_size too large for the modulus switch");   // ms() reads the top 32 bits
+    const size_t tiles = ((lwe_dim + PBS_TILE) / PBS_TILE) * ((batch + PBS_TILE - 1) / PBS_TILE);
+    const hipError_t e = launch_native_lwe_modswitch(pl->info.word, rot_t, lwe, native_logn(pl), lwe_dim, batch, ew_grid(tiles * 256), st);
+    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_lwe_modswitch_kernel launch failed: %s", hipGetErrorString(e));
+    return CNTT_OK;
+}
+static int native_extract_device(const cntt_native *pl, void *lwe_out, const void *glwe, size_t glwe_dim, size_t index, size_t batch,
+                                 hipStream_t st) {
+    const hipError_t e = launch_native_sample_extract(pl->info.word, lwe_out, glwe, native_logn(pl), glwe_dim, (uint32_t)index, batch,
+                                                      ew_grid(batch * (glwe_dim * pl->n + 1)), st);
+    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_sample_extract_kernel launch failed: %s", hipGetErrorString(e));
+    return CNTT_OK;
+}
+// acc = X^(body row of rot_t) lut, then lwe_dim times decomposition (CMux difference) into `digits` and the external product accumulating
+// into acc.  In place is sound: the digits are complete before the product starts (stream order), the product reads only the digits and
+// the key, and each of its launches of two outputs reads and writes only its own outputs.
+static int native_blind_rotate_device(const cntt_native *pl, void *acc, const void *lut, bool lut_per_element, const uint32_t *rot_t,
+                                      const void *const *bsk, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels,
+                                      size_t batch, void *digits, hipStream_t st) {
+    const size_t npolys = glwe_dim + 1, nterms = npolys * levels, n = pl->n, w = (size_t)pl->info.word;
+    const size_t slice = nterms * npolys * n * pl->rbytes();   // one iteration's key, bytes per plane
+    const hipError_t e = launch_native_pbs_init(pl->info.word, acc, lut, rot_t + lwe_dim * batch, native_logn(pl), (uint32_t)npolys,
+                                                lut_per_element, batch, batch * npolys * n * w > STREAM_BYTES,
+                                                ew_grid(batch * npolys * n * w / 16), st);
+    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_pbs_init_kernel launch failed: %s", hipGetErrorString(e));
+    const int k = pl->info.nprimes;
+    const void *key[10];
+    for (size_t i = 0; i < lwe_dim; ++i) {
+        for (int j = 0; j < k; ++j) key[j] = static_cast<const char *>(bsk[j]) + i * slice;
+        if (int rc = native_gadget_device(pl, digits, acc, rot_t + i * batch, npolys, base_log, levels, CNTT_SRC_CMUX, batch, st)) return rc;
+        if (int rc = native_ext_device(pl, acc, digits, key, nterms, npolys, batch, true, st)) return rc;
+    }
+    return CNTT_OK;
+}
+
+extern "C" int cntt_native_lwe_modswitch_batch(const cntt_native_t *pl, uint32_t *rot_t, const void *lwe, size_t lwe_dim, size_t batch,
+                                               cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (batch == 0) return CNTT_OK;
+    if (!rot_t) return fail(CNTT_EINVAL, "rot_t is NULL");
+    if (!lwe) return fail(CNTT_EINVAL, "lwe is NULL");
+    const size_t rb = (lwe_dim + 1) * batch * sizeof(uint32_t), lb = (lwe_dim + 1) * batch * (size_t)pl->info.word;
+    if (ranges_overlap(rot_t, rb, lwe, lb)) return fail(CNTT_EINVAL, "rot_t overlaps lwe");
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) return native_modswitch_device(pl, rot_t, lwe, lwe_dim, batch, st);
+    Staging s(st);
+    uint32_t *dr = (uint32_t *)s.out(rot_t, rb);
+    const void *dl = s.in(lwe, lb);
+    if (int rc = s.status()) return rc;
+    if (int rc = native_modswitch_device(pl, dr, dl, lwe_dim, batch, st)) return rc;
+    return s.finish();
+}
+
+extern "C" int cntt_native_sample_extract_batch(const cntt_native_t *pl, void *lwe_out, const void *glwe, size_t glwe_dim, size_t index,
+                                                size_t batch, cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (index >= pl->n) return fail(CNTT_EINVAL, "index = %zu is not below ntt_size = %zu", index, pl->n);
+    if (batch == 0) return CNTT_OK;
+    if (!lwe_out) return fail(CNTT_EINVAL, "lwe_out is NULL");
+    if (!glwe) return fail(CNTT_EINVAL, "glwe is NULL");
+    const size_t w = (size_t)pl->info.word, ob = batch * (glwe_dim * pl->n + 1) * w, gb = batch * (glwe_dim + 1) * pl->n * w;
+    if (ranges_overlap(lwe_out, ob, glwe, gb)) return fail(CNTT_EINVAL, "lwe_out overlaps glwe");
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) return native_extract_device(pl, lwe_out, glwe, glwe_dim, index, batch, st);
+    Staging s(st);
+    void *dout = s.out(lwe_out, ob);
+    const void *dg = s.in(glwe, gb);
+    if (int rc = s.status()) return rc;
+    if (int rc = native_extract_device(pl, dout, dg, glwe_dim, index, batch, st)) return rc;
+    return s.finish();
+}
+
+// the argument checks blind_rotate and bootstrap share, up to the NULL key planes; `need` = what the workspace must hold
+static int pbs_check(const cntt_native *pl, const void *const *bsk, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels,
+                     size_t batch, const void *workspace, size_t workspace_bytes, size_t need) {
+    const uint32_t some_rot = 0;
+    if (int rc = gadget_check(pl, base_log, levels, CNTT_SRC_CMUX, &some_rot)) return rc;
+    if (glwe_dim + 1 >= ((size_t)1 << 32)) return fail(CNTT_EINVAL, "glwe_dim too large");
+    const size_t nterms = (glwe_dim + 1) * levels;
+    if (nterms > pl->max_terms)
+        return fail(CNTT_EINVAL, "(glwe_dim + 1) * levels = %zu exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range",
+                    nterms, pl->max_terms);
+    if (batch == 0) return CNTT_OK;
+    if (lwe_dim) {
+        if (!bsk) return fail(CNTT_EINVAL, "bsk_ntt is NULL");
+        if (int rc = check_key_planes(pl, bsk, "bsk_ntt")) return rc;
+    }
+    if (workspace) {
+        if ((uintptr_t)workspace % 16) return fail(CNTT_EINVAL, "workspace is not 16-byte aligned");
+        if (workspace_bytes < need) return fail(CNTT_EINVAL, "workspace_bytes = %zu is below the %zu bytes this call needs", workspace_bytes, need);
+    }
+    return CNTT_OK;
+}
+extern "C" int cntt_native_blind_rotate_batch(const cntt_native_t *pl, void *acc, const void *lut, int lut_per_element, const uint32_t *rot_t,
+                                              const void *const *bsk_ntt, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels,
+                                              size_t batch, void *workspace, size_t workspace_bytes, cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (batch && !rot_t) return fail(CNTT_EINVAL, "rot_t is NULL");
+    const PbsSizes Z = pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch);
+    if (int rc = pbs_check(pl, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, Z.digits)) return rc;
+    if (batch == 0) return CNTT_OK;
+    if (!acc) return fail(CNTT_EINVAL, "acc is NULL");
+    if (!lut) return fail(CNTT_EINVAL, "lut is NULL");
+    const size_t lb = lut_per_element ? Z.acc : Z.acc / batch;
+    if (ranges_overlap(acc, Z.acc, lut, lb)) return fail(CNTT_EINVAL, "acc overlaps lut");
+    if (ranges_overlap(acc, Z.acc, rot_t, Z.rot)) return fail(CNTT_EINVAL, "acc overlaps rot_t");
+    if (workspace && ranges_overlap(acc, Z.acc, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "acc overlaps workspace");
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) {
+        void *digits = workspace;
+        if (!digits && lwe_dim) HIP_TRY(hipMallocAsync(&digits, Z.digits, st));   // one allocation for the whole loop
+        const int rc = native_blind_rotate_device(pl, acc, lut, lut_per_element != 0, rot_t, bsk_ntt, lwe_dim, glwe_dim, base_log, levels,
+                                                  batch, digits, st);
+        if (!workspace && digits) (void)hipFreeAsync(digits, st);
+        return rc;
+    }
+    if (int rc = check_rot_host(pl, rot_t, (lwe_dim + 1) * batch, "rot_t")) return rc;
+    const size_t kb = lwe_dim * (glwe_dim + 1) * levels * (glwe_dim + 1) * pl->n * pl->rbytes();
+    Staging s(st);
+    const void *dkey[10];
+    if (lwe_dim) key_planes_to_device(pl, s, bsk_ntt, kb, dkey);
+    const void *dlut = s.in(lut, lb);
+    const uint32_t *drot = (const uint32_t *)s.in(rot_t, Z.rot);
+    void *dacc = s.out(acc, Z.acc), *ddig = s.alloc(Z.digits);
+    if (int rc = s.status()) return rc;
+    if (int rc = native_blind_rotate_device(pl, dacc, dlut, lut_per_element != 0, drot, dkey, lwe_dim, glwe_dim, base_log, levels, batch, ddig, st))
+        return rc;
+    return s.finish();
+}
+
+// modulus switch -> blind rotation -> extraction of coefficient 0 on device buffers; ws holds digits | rot_t | acc (PbsSizes)
+static int native_bootstrap_device(const cntt_native *pl, void *lwe_out, const void *lwe_in, const void *lut, bool lut_per_element,
+                                   const void *const *bsk, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels, size_t batch,
+                                   const PbsSizes &Z, char *ws, hipStream_t st) {
+    uint32_t *rot_t = reinterpret_cast<uint32_t *>(ws + up256(Z.digits));
+    void *acc = ws + up256(Z.digits) + up256(Z.rot);
+    if (int rc = native_modswitch_device(pl, rot_t, lwe_in, lwe_dim, batch, st)) return rc;
+    if (int rc = native_blind_rotate_device(pl, acc, lut, lut_per_element, rot_t, bsk, lwe_dim, glwe_dim, base_log, levels, batch, ws, st))
+        return rc;
+    return native_extract_device(pl, lwe_out, acc, glwe_dim, 0, batch, st);
+}
+
+extern "C" int cntt_native_bootstrap_batch(const cntt_native_t *pl, void *lwe_out, const void *lwe_in, const void *lut, int lut_per_element,
+                                           const void *const *bsk_ntt, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels,
+                                           size_t batch, void *workspace, size_t workspace_bytes, cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    const PbsSizes Z = pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch);
+    if (int rc = pbs_check(pl, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, Z.total())) return rc;
+    if (batch == 0) return CNTT_OK;
+    if (!lwe_out) return fail(CNTT_EINVAL, "lwe_out is NULL");
+    if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
+    if (!lut) return fail(CNTT_EINVAL, "lut is NULL");
+    const size_t w = (size_t)pl->info.word, ob = batch * (glwe_dim * pl->n + 1) * w, ib = batch * (lwe_dim + 1) * w;
+    const size_t lb = lut_per_element ? Z.acc : Z.acc / batch;
+    if (ranges_overlap(lwe_out, ob, lwe_in, ib)) return fail(CNTT_EINVAL, "lwe_out overlaps lwe_in");
+    if (ranges_overlap(lwe_out, ob, lut, lb)) return fail(CNTT_EINVAL, "lwe_out overlaps lut");
+    if (workspace) {
+        if (ranges_overlap(lwe_out, ob, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_out overlaps workspace");
+        if (ranges_overlap(lwe_in, ib, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_in overlaps workspace");
+        if (ranges_overlap(lut, lb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lut overlaps workspace");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) {
+        void *ws = workspace;
+        if (!ws) HIP_TRY(hipMallocAsync(&ws, Z.total(), st));   // one allocation for the whole call
+        const int rc = native_bootstrap_device(pl, lwe_out, lwe_in, lut, lut_per_element != 0, bsk_ntt, lwe_dim, glwe_dim, base_log, levels,
+                                               batch, Z, static_cast<char *>(ws), st);
+        if (!workspace) (void)hipFreeAsync(ws, st);
+        return rc;
+    }
+    const size_t kb = lwe_dim * (glwe_dim + 1) * levels * (glwe_dim + 1) * pl->n * pl->rbytes();
+    Staging s(st);
+    const void *dkey[10];
+    if (lwe_dim) key_planes_to_device(pl, s, bsk_ntt, kb, dkey);
+    const void *din = s.in(lwe_in, ib), *dlut = s.in(lut, lb);
+    void *dout = s.out(lwe_out, ob), *dws = s.alloc(Z.total());
+    if (int rc = s.status()) return rc;
+    if (int rc = native_bootstrap_device(pl, dout, din, dlut, lut_per_element != 0, dkey, lwe_dim, glwe_dim, base_log, levels, batch, Z,
+                                         static_cast<char *>(dws), st))
+        return rc;
+    return s.finish();
+}

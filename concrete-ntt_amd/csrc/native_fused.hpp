@@ -14,7 +14,7 @@
 
 namespace cntt {
 
-// digit structure of the reference plans handled here (host.hip NATIVE_KINDS; kind numbers of cntt_native_kind_t)
+// digit structure of the reference plans handled here (host_native.hip NATIVE_KINDS; kind numbers of cntt_native_kind_t)
 template <int KIND> struct NativeShape;
 struct alignas(16) Word128 {  // u128 as Rust lays it out on x86-64: 16-byte little-endian (lo, hi)
     uint64_t lo, hi;
@@ -350,7 +350,7 @@ __device__ __forceinline__ void native_product(typename NativeShape<KIND>::W *__
 //     frac += hi32(gamma_i * floor(2^59 / P_i))            (27 fractional bits: the sum is within 2^-5.9 + 2^-22 of k)
 // (the pointwise product between the transforms is a lazy Montgomery product, acc_mont_lazy: its 2^-32 rides in the same constants)
 // and at the end  out = acc - ((frac + 2^26) >> 27) * (M mod 2^bits(W)).  The factor (M / P_i)^-1 rides in the constants of
-// the inverse transform's last stage next to 1 / n (Bfly::inv_norm: host.hip folds it into F.P[i].n_inv / last_w), so gamma_i
+// the inverse transform's last stage next to 1 / n (Bfly::inv_norm: host_native.hip folds it into F.P[i].n_inv / last_w), so gamma_i
 // IS the transform's lazy output: no canonicalisation, no multiplication.  State per coefficient: one W-wide word and one
 // 32-bit word in registers instead of k - 1 parked residues; LDS holds the exchange buffer only.
 // The residue split is lazy too ([0, 2 P_i): all the first butterfly stage needs): 2^32 = c_i (mod P_i) with c_i < 2^26 for
@@ -375,7 +375,7 @@ __device__ __forceinline__ uint32_t acc_red58(uint64_t t, uint32_t p, uint32_t m
 // a * b / 2^32 mod p in [0, 2p) for lazy a, b in [0, 4p), p < 2^30 (Montgomery; pinv_neg = -p^-1 mod 2^32): each operand takes one
 // conditional subtraction of 2p (a b < 4 p^2 < 2^62, t + m p < 2^63, u < p^2 / 2^30 + p < 2p) -- seven instructions where the
 // canonical route (two canonicalisations + Barrett, mul_for_inv) takes thirteen.  The factor 2^-32 is undone by the constants of the
-// inverse transform's last stage (host.hip, build_acc_args).
+// inverse transform's last stage (host_native.hip, build_acc_args).
 __device__ __forceinline__ uint32_t acc_mont_lazy(uint32_t a, uint32_t b, const ModParams<uint32_t> &P) {
     a = umin<uint32_t>(a, a - P.two_p);
     b = umin<uint32_t>(b, b - P.two_p);

@@ -2,8 +2,8 @@
 //     native_lwe_modswitch_kernel    LWE words -> exponents below 2n, transposed so that every iteration's `rot` is contiguous
 //     native_pbs_init_kernel         acc[b][p] = X^(rot[b]) lut[p]        (the gather of native_gadget_kernel's rotate mode, no digits)
 //     native_sample_extract_kernel   GLWE -> LWE of dimension k n: a reversed, negated copy per mask polynomial plus the body word
-// The loop between them is host code (host.hip, native_blind_rotate_device) over the r7 decomposition kernel and the r6 external
-// product, which this file does not touch.  The kernels are instantiated in native_pbs.hip; host.hip sees the launchers only.
+// The loop between them is host code (host_native_ext.hip, native_blind_rotate_device) over the r7 decomposition kernel and the r6 external
+// product, which this file does not touch.  The kernels are instantiated in native_pbs.hip; host_native_ext.hip sees the launchers only.
 #pragma once
 #include "native_gadget.hpp"
 

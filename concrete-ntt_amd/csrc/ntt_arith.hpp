@@ -65,7 +65,7 @@ template <class T> struct ModParams {
     // product between the transforms is a Montgomery product there (mul_fused) and leaves a factor 2^-B for the last inverse stage
     T mont_n_inv, mont_n_inv_shoup, mont_last_w, mont_last_w_shoup;
     T mont_r, mont_r_shoup;   // 2^B mod p and its Shoup companion: the fused mul_accumulate chains undo their products' 2^-B with it
-    // set per LAUNCH by the host (0 in the plan): the batch of this call is larger than STREAM_BYTES (host.hip, 384 MiB) and passes through the
+    // set per LAUNCH by the host (0 in the plan): the batch of this call is larger than STREAM_BYTES (host_common.hpp, 384 MiB) and passes through the
     // chip once -- the stand-alone transform kernels then put the non-temporal hint on their tile loads and stores (ntt_kernel.hpp)
     uint32_t stream;
 };
@@ -415,7 +415,7 @@ template <int CLS> struct BoxOps {
 //   inverse  (x, y) <- (x + y, (x - y) w): sums double, products come back below p
 //     H = 8: inputs <= 1 give 2, then 4 -> the sums are reduced after every SECOND stage (|x - y| <= 4 always);
 //     H = 4: the sums are reduced after EVERY stage (inputs <= 1, |x + y| <= 2, |x - y| <= 2, products <= 1).
-// Twiddles come from a table of (c, c/p) doubles built by the host (csrc/host.hip); the public values are the same
+// Twiddles come from a table of (c, c/p) doubles built by the host (csrc/host_prime.hip); the public values are the same
 // canonical integers as in every other class: the load turns a canonical word into a double (two instructions) and
 // the store reduces, lifts negatives by p and extracts the integer (nine).
 // ---------------------------------------------------------------------------------------------
@@ -504,7 +504,7 @@ __host__ __device__ constexpr bool is_fp_class(int cls) { return cls == CLS_FP |
 // an exact integer v = residue (mod p).  Memory holds canonical words; LDS between the passes holds the CENTRED residue
 // (|v| <= (p + 1) / 2 < 2^31) as an int32 bit pattern, so a pass boundary costs v_cvt_f64_i32 on the way in and
 // reduce + v_cvt_i32_f64 on the way out.  A twiddle-table entry (8 bytes, like every TwPair<uint32_t>) IS the centred
-// twiddle as a double (csrc/host.hip): no conversion, and no quotient companion -- the quotient comes from the product,
+// twiddle as a double (csrc/host_prime.hip): no conversion, and no quotient companion -- the quotient comes from the product,
 //     h = fl(y c)   q = rint(fl(h / p))   l = fma(y, c, -h)   r = fma(-q, p, h)   t = r + l        (Fp::mul_data)
 // eight instructions per butterfly with the two sums.
 // With p < 2^32 the doubles have H = 2^53 / p > 2^21 units of p of headroom, so NO range reduction is needed inside a

@@ -162,7 +162,7 @@ struct NttKernel {
 
     // ---- tile-relative global addressing (persistent kernels) -----------------------------------
     // NT (round 5): the non-temporal hint for batches that stream through the chip once (more than STREAM_BYTES = 384 MiB,
-    // past the 256 MiB Infinity Cache: ModParams::stream, decided per launch by host.hip).  On the asynchronous tile loads AND the tile stores of the stand-alone
+    // past the 256 MiB Infinity Cache: ModParams::stream, decided per launch by host_prime.hip).  On the asynchronous tile loads AND the tile stores of the stand-alone
     // transforms together it is worth -3 % (either alone nothing; nothing in the fused product, whose rhs loads are synchronous and get
     // slower with it: profiles/r05_nt_hint_ab.txt, r05_nt_headline_ab.txt); on a batch that fits the cache it costs 3 ... 6 %, because the
     // next kernel then finds nothing there (profiles/r05_small_batch_ab.txt).  The plan tables always keep the default policy.

@@ -9,7 +9,7 @@
 namespace cntt {
 // The ONE switchboard behind cntt_debug_set() / cntt_debug_get() (include/cntt.h, "testing only"): kernel-selection overrides for A/B
 // timing and for the parity tests that compare two device paths.  Results are identical either way; nothing in the library reads the
-// process environment.  -1 = the library's own choice.  Defined in host.hip.
+// process environment.  -1 = the library's own choice.  Defined in host_core.hip.
 enum DebugSwitch : int {
     DBG_FP = 0,         // 1 (default): double-precision classes for u64 p < 2^51 / u32 p >= 2^31; 0: integer butterflies.  Read at plan creation.
     DBG_PM64,           // 1 (default): fold-by-c class for p = 2^64 - c; 0: Montgomery class.  Read at plan creation.

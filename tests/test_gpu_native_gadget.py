@@ -20,7 +20,7 @@ KINDS = {"native32_plan32": native32.Plan32, "native64_plan32": native64.Plan32,
          "native_binary64_plan52": native_binary64.Plan52}
 FUSED = ["native32_plan32", "native64_plan32", "native_binary32_plan32", "native_binary64_plan32"]
 MODES = ["plain", "rotate", "cmux"]
-STREAM_BYTES = 384 << 20   # the library's streaming threshold (host.hip)
+STREAM_BYTES = 384 << 20   # the library's streaming threshold (host_common.hpp)
 
 
 def _torch():

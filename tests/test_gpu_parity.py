@@ -874,7 +874,7 @@ def test_native_polymul_large_n(oracle, kind, n):
 def test_native_polymul_streams_and_threads_share_a_plan(kind, n, batch):
     """One plan, one workspace (parking area of the persistent kernel / residue arrays of the composed pipeline), used from
     two HIP streams and from two host threads at once: the library orders the calls that share the workspace
-    (csrc/host.hip, Workspace), so every result equals the one computed alone."""
+    (csrc/host_native.hip, Workspace), so every result equals the one computed alone."""
     import threading
     torch = _torch()
     cls = NATIVE[kind]

@@ -1,7 +1,7 @@
 """The NON-TEMPORAL branches (round 5) in every device arithmetic class, and byte offsets past 2^32 on 64-bit words in the
 persistent walk.
 
-csrc/host.hip decides per call whether a batch streams through the chip: ntt_device sets ModParams::stream when the batch is larger
+csrc/host_prime.hip decides per call whether a batch streams through the chip: ntt_device sets ModParams::stream when the batch is larger
 than STREAM_BYTES, and the wp / blk walks then load and store through gather_async_rt / issue_rt / scatter_tile_rt with nt = true
 (csrc/ntt_kernel.hpp, csrc/ntt_blk.hpp); pointwise_device runs pointwise_kernel<T, OP, true> when NARR x count x word exceeds it
 (NARR = 1 normalize, 2 mul_assign_normalize, 3 mul_accumulate).  Every case runs the FIRST size that streams:
@@ -28,7 +28,7 @@ def _host(t, dtype):
 
 
 def streamed_batch(bits, n):
-    """the first batch that streams: batch x N x word > STREAM_BYTES (csrc/host.hip ntt_device)"""
+    """the first batch that streams: batch x N x word > STREAM_BYTES (csrc/host_prime.hip ntt_device)"""
     w = bits // 8
     batch = STREAM_BYTES // (n * w) + 1
     assert batch * n * w > STREAM_BYTES and (batch - 1) * n * w <= STREAM_BYTES
@@ -81,7 +81,7 @@ PW_CASES = [(bits, name, p, cls, op, narr) for (bits, name, p, cls) in PRIMES fo
 
 @pytest.mark.parametrize("bits,name,p,cls,op,narr", PW_CASES, ids=["u%d-%s-%s" % (b, nm, op) for (b, nm, _, _, op, _) in PW_CASES])
 def test_gpu_streamed_pointwise(oracle, bits, name, p, cls, op, narr):
-    """host slices of any length go through pointwise_device as they are (csrc/host.hip prime_op): an odd count past the rule"""
+    """host slices of any length go through pointwise_device as they are (csrc/host_prime.hip prime_op): an odd count past the rule"""
     p = prime_of(oracle, p)
     plan, oplan = make_plans(oracle, bits, 1024, p, cls)
     w = bits // 8

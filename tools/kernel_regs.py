@@ -30,7 +30,7 @@ def kernels(unit, tmp):
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     show_all = "--all" in sys.argv
-    units = args or sorted(f[:-2] for f in os.listdir(OBJ) if f.endswith(".o") and f != "host.o")
+    units = args or sorted(f[:-2] for f in os.listdir(OBJ) if f.endswith(".o"))
     with tempfile.TemporaryDirectory() as tmp:
         for u in units:
             for name, vg, sg, sp, scratch, lds in kernels(u, tmp):
