@@ -1,10 +1,11 @@
 // libcntt_hip.so host side, what is built on the native plans without a counterpart in the reference: the external product
 // (include/cntt_ext.h), rotation / gadget decomposition and the external product on undecomposed polynomials (include/cntt_gadget.h),
-// the programmable bootstrap (include/cntt_pbs.h).
+// the programmable bootstrap (include/cntt_pbs.h), the LWE keyswitch and keyswitch + bootstrap (include/cntt_keyswitch.h).
 #include <cstdio>
 
 #include "host_common.hpp"
 #include "native_gadget.hpp"
+#include "native_keyswitch.hpp"
 #include "native_pbs.hpp"
 
 // ---------------------------------------------------------------------------------------------
@@ -515,5 +516,115 @@ extern "C" int cntt_native_bootstrap_batch(const cntt_native_t *pl, void *lwe_ou
     if (int rc = native_bootstrap_device(pl, dout, din, dlut, lut_per_element != 0, dkey, lwe_dim, glwe_dim, base_log, levels, batch, Z,
                                          static_cast<char *>(dws), st))
         return rc;
+    return s.finish();
+}
+
+// ---------------------------------------------------------------------------------------------
+// LWE keyswitch, and keyswitch + bootstrap in one call (include/cntt_keyswitch.h, native_keyswitch.hpp)
+// ---------------------------------------------------------------------------------------------
+// the digit and stride checks the two calls share; `pre` = "" or "ks_": how the combined call names the keyswitch's digit arguments
+static int keyswitch_check(const cntt_native *pl, size_t lwe_dim_out, size_t row_stride, unsigned base_log, unsigned levels, const char *pre) {
+    const unsigned wbits = 8u * (unsigned)pl->info.word;
+    if (base_log == 0) return fail(CNTT_EINVAL, "%sbase_log is 0", pre);
+    if (levels == 0) return fail(CNTT_EINVAL, "%slevels is 0", pre);
+    if ((uint64_t)base_log * levels > wbits)
+        return fail(CNTT_EINVAL, "%sbase_log * %slevels = %u * %u exceeds the word width %u", pre, pre, base_log, levels, wbits);
+    if (base_log > 31) return fail(CNTT_EINVAL, "%sbase_log = %u exceeds 31: the keyswitch keeps a digit in one 32-bit register", pre, base_log);
+    if (row_stride < lwe_dim_out + 1)
+        return fail(CNTT_EINVAL, "row_stride = %zu is below lwe_dim_out + 1 = %zu words", row_stride, lwe_dim_out + 1);
+    return CNTT_OK;
+}
+// bytes of a key of `rows` rows: the last row needs its lwe_dim_out + 1 words only
+static size_t ksk_bytes(const cntt_native *pl, size_t rows, size_t lwe_dim_out, size_t row_stride) {
+    return rows ? ((rows - 1) * row_stride + lwe_dim_out + 1) * (size_t)pl->info.word : 0;
+}
+static int native_keyswitch_device(const cntt_native *pl, void *out, const void *in, const void *ksk, size_t lin, size_t lout,
+                                   size_t row_stride, unsigned base_log, unsigned levels, size_t batch, hipStream_t st) {
+    const u128 off = gadget_offset(8u * (unsigned)pl->info.word, base_log, levels);
+    const hipError_t e = launch_native_keyswitch(pl->info.word, out, in, ksk, (uint64_t)off, (uint64_t)(off >> 64), base_log, levels, lin, lout,
+                                                 row_stride, batch, st);
+    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_keyswitch_kernel launch failed: %s", hipGetErrorString(e));
+    return CNTT_OK;
+}
+
+extern "C" int cntt_native_keyswitch_batch(const cntt_native_t *pl, void *lwe_out, const void *lwe_in, const void *ksk, size_t lwe_dim_in,
+                                           size_t lwe_dim_out, size_t row_stride, unsigned base_log, unsigned levels, size_t batch,
+                                           cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (int rc = keyswitch_check(pl, lwe_dim_out, row_stride, base_log, levels, "")) return rc;
+    if (batch == 0) return CNTT_OK;
+    if (!lwe_out) return fail(CNTT_EINVAL, "lwe_out is NULL");
+    if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
+    if (lwe_dim_in && !ksk) return fail(CNTT_EINVAL, "ksk is NULL");
+    const size_t w = (size_t)pl->info.word, ob = batch * (lwe_dim_out + 1) * w, ib = batch * (lwe_dim_in + 1) * w;
+    const size_t kb = ksk_bytes(pl, lwe_dim_in * levels, lwe_dim_out, row_stride);
+    if (ranges_overlap(lwe_out, ob, lwe_in, ib)) return fail(CNTT_EINVAL, "lwe_out overlaps lwe_in");
+    if (ranges_overlap(lwe_out, ob, ksk, kb)) return fail(CNTT_EINVAL, "lwe_out overlaps ksk");
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE)
+        return native_keyswitch_device(pl, lwe_out, lwe_in, ksk, lwe_dim_in, lwe_dim_out, row_stride, base_log, levels, batch, st);
+    Staging s(st);
+    void *dout = s.out(lwe_out, ob);
+    const void *din = s.in(lwe_in, ib), *dk = s.in(ksk, kb);
+    if (int rc = s.status()) return rc;
+    if (int rc = native_keyswitch_device(pl, dout, din, dk, lwe_dim_in, lwe_dim_out, row_stride, base_log, levels, batch, st)) return rc;
+    return s.finish();
+}
+
+// bytes of the keyswitched ciphertexts, which follow the bootstrap's part of the workspace (cntt_keyswitch.h states the formula)
+static size_t ks_mid_bytes(const cntt_native *pl, size_t lwe_dim, size_t batch) { return batch * (lwe_dim + 1) * (size_t)pl->info.word; }
+extern "C" size_t cntt_native_ks_pbs_workspace_bytes(const cntt_native_t *pl, size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) {
+    return pl ? pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch).total() + up256(ks_mid_bytes(pl, lwe_dim, batch)) : 0;
+}
+
+extern "C" int cntt_native_keyswitch_bootstrap_batch(const cntt_native_t *pl, void *lwe_out, const void *lwe_in, const void *ksk,
+                                                     size_t row_stride, unsigned ks_base_log, unsigned ks_levels, const void *lut,
+                                                     int lut_per_element, const void *const *bsk_ntt, size_t lwe_dim, size_t glwe_dim,
+                                                     unsigned base_log, unsigned levels, size_t batch, void *workspace, size_t workspace_bytes,
+                                                     cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (int rc = keyswitch_check(pl, lwe_dim, row_stride, ks_base_log, ks_levels, "ks_")) return rc;
+    const PbsSizes Z = pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch);
+    const size_t mid = ks_mid_bytes(pl, lwe_dim, batch), need = Z.total() + up256(mid);
+    if (int rc = pbs_check(pl, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, need)) return rc;
+    if (batch == 0) return CNTT_OK;
+    if (!lwe_out) return fail(CNTT_EINVAL, "lwe_out is NULL");
+    if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
+    if (!lut) return fail(CNTT_EINVAL, "lut is NULL");
+    const size_t big = glwe_dim * pl->n;   // the dimension of both ends
+    if (big && !ksk) return fail(CNTT_EINVAL, "ksk is NULL");
+    const size_t w = (size_t)pl->info.word, eb = batch * (big + 1) * w, kb = ksk_bytes(pl, big * ks_levels, lwe_dim, row_stride);
+    const size_t lb = lut_per_element ? Z.acc : Z.acc / batch;
+    if (ranges_overlap(lwe_out, eb, lwe_in, eb)) return fail(CNTT_EINVAL, "lwe_out overlaps lwe_in");
+    if (ranges_overlap(lwe_out, eb, ksk, kb)) return fail(CNTT_EINVAL, "lwe_out overlaps ksk");
+    if (ranges_overlap(lwe_out, eb, lut, lb)) return fail(CNTT_EINVAL, "lwe_out overlaps lut");
+    if (workspace) {
+        if (ranges_overlap(lwe_out, eb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_out overlaps workspace");
+        if (ranges_overlap(lwe_in, eb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_in overlaps workspace");
+        if (ranges_overlap(ksk, kb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "ksk overlaps workspace");
+        if (ranges_overlap(lut, lb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lut overlaps workspace");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // keyswitch into the tail of the workspace, bootstrap from there with the head
+    auto run = [&](void *out, const void *in, const void *key, const void *table, const void *const *bsk, char *ws) {
+        void *lwe_mid = ws + Z.total();
+        if (int rc = native_keyswitch_device(pl, lwe_mid, in, key, big, lwe_dim, row_stride, ks_base_log, ks_levels, batch, st)) return rc;
+        return native_bootstrap_device(pl, out, lwe_mid, table, lut_per_element != 0, bsk, lwe_dim, glwe_dim, base_log, levels, batch, Z, ws, st);
+    };
+    if (where == CNTT_MEM_DEVICE) {
+        void *ws = workspace;
+        if (!ws) HIP_TRY(hipMallocAsync(&ws, need, st));   // one allocation for the whole call
+        const int rc = run(lwe_out, lwe_in, ksk, lut, bsk_ntt, static_cast<char *>(ws));
+        if (!workspace) (void)hipFreeAsync(ws, st);
+        return rc;
+    }
+    const size_t bb = lwe_dim * (glwe_dim + 1) * levels * (glwe_dim + 1) * pl->n * pl->rbytes();
+    Staging s(st);
+    const void *dkey[10];
+    if (lwe_dim) key_planes_to_device(pl, s, bsk_ntt, bb, dkey);
+    const void *din = s.in(lwe_in, eb), *dk = s.in(ksk, kb), *dlut = s.in(lut, lb);
+    void *dout = s.out(lwe_out, eb), *dws = s.alloc(need);
+    if (int rc = s.status()) return rc;
+    if (int rc = run(dout, din, dk, dlut, dkey, static_cast<char *>(dws))) return rc;
     return s.finish();
 }

@@ -236,6 +236,24 @@ template <cntt_native_kind_t KIND, class R, int NPRIMES, int WORD_BYTES> class N
         check(cntt_native_bootstrap_batch(h_, lwe_out, lwe_in, lut, lut_per_element ? 1 : 0, bsk_ntt, lwe_dim, glwe_dim, base_log, levels,
                                           batch, workspace, workspace_bytes, where, stream));
     }
+    // LWE keyswitch (cntt_keyswitch.h) from lwe_dim_in to lwe_dim_out, and keyswitch (glwe_dim * n -> lwe_dim) + bootstrap in one call
+    void keyswitch_batch(void *lwe_out, const void *lwe_in, const void *ksk, size_t lwe_dim_in, size_t lwe_dim_out, size_t row_stride,
+                         unsigned base_log, unsigned levels, size_t batch, cntt_mem_t where = CNTT_MEM_DEVICE,
+                         void *stream = nullptr) const {
+        check(cntt_native_keyswitch_batch(h_, lwe_out, lwe_in, ksk, lwe_dim_in, lwe_dim_out, row_stride, base_log, levels, batch, where,
+                                          stream));
+    }
+    size_t ks_pbs_workspace_bytes(size_t lwe_dim, size_t glwe_dim, unsigned levels_bsk, size_t batch) const {
+        return cntt_native_ks_pbs_workspace_bytes(h_, lwe_dim, glwe_dim, levels_bsk, batch);
+    }
+    void keyswitch_bootstrap_batch(void *lwe_out, const void *lwe_in, const void *ksk, size_t row_stride, unsigned ks_base_log,
+                                   unsigned ks_levels, const void *lut, bool lut_per_element, const void *const *bsk_ntt, size_t lwe_dim,
+                                   size_t glwe_dim, unsigned base_log, unsigned levels, size_t batch, void *workspace = nullptr,
+                                   size_t workspace_bytes = 0, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(cntt_native_keyswitch_bootstrap_batch(h_, lwe_out, lwe_in, ksk, row_stride, ks_base_log, ks_levels, lut,
+                                                    lut_per_element ? 1 : 0, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace,
+                                                    workspace_bytes, where, stream));
+    }
 };
 }  // namespace detail
 

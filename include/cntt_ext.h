@@ -59,4 +59,8 @@ size_t cntt_native_max_terms(const cntt_native_t *plan);
  * call -- is declared the same way, through a file of its own that carries the conventions. */
 #include "cntt_pbs.h"
 
+/* The LWE keyswitch that takes a bootstrap's output back to the dimension the next one takes, and keyswitch + bootstrap in one call
+ * that chains with itself, likewise. */
+#include "cntt_keyswitch.h"
+
 #endif /* CNTT_EXT_H */

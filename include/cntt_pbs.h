@@ -2,7 +2,8 @@
  * on the device -- modulus switch of the LWE words, accumulator set-up, the blind rotation loop in place, sample extraction -- as
  * four calls, and one call that runs them all.  The loop runs the kernels of cntt_gadget.h (CNTT_SRC_CMUX decomposition) and of
  * cntt_native_external_product_batch (accumulate = 1) once per LWE mask word, into ONE accumulator and ONE digit scratch.  No
- * counterpart in the reference.  No keyswitch, no key or noise generation: the caller brings the keys.  Plain C11.
+ * counterpart in the reference.  The keyswitch back to dimension L, alone and in one call with the bootstrap, is in cntt_keyswitch.h.
+ * No key or noise generation: the caller brings the keys.  Plain C11.
  *
  * Symbols: w = word width of the plan's kind (32, 64, 128), n = ntt_size = 2^logn, k = glwe_dim, L = lwe_dim.
  *

@@ -1,0 +1,342 @@
+"""C ABI of the LWE keyswitch (include/cntt_keyswitch.h through include/cntt_ext.h): the header is plain C11, the three names are
+declared through cntt_ext.h and exported, cntt.h keeps its 87 entry points, cntt_ext.h's own text its 2 and cntt_pbs.h its 5, every
+CNTT_EINVAL case is refused on host buffers by the argument checks that precede any device call (outputs untouched, argument named),
+ks_pbs_workspace_bytes is the header's formula, the Python wrappers panic on bad shapes, the code object of the new unit has no
+scratch and no spills -- and the plain-int model of the keyswitch that tests/test_gpu_native_keyswitch.py compares the kernel with is
+itself checked here against the phase identity the header states.  No GPU needed."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import concrete_ntt_amd as cntt
+from concrete_ntt_amd import native32, native64, native128
+from concrete_ntt_amd._lib import EINVAL
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXT = os.path.join(ROOT, "include", "cntt_ext.h")
+PBS = os.path.join(ROOT, "include", "cntt_pbs.h")
+KS = os.path.join(ROOT, "include", "cntt_keyswitch.h")
+HEADER = os.path.join(ROOT, "include", "cntt.h")
+NEW = {"cntt_native_keyswitch_batch", "cntt_native_keyswitch_bootstrap_batch", "cntt_native_ks_pbs_workspace_bytes"}
+
+
+# -- the model (restated in tests/test_gpu_native_keyswitch.py) -----------------------------------------------------------------------
+def digits(x, w, beta, ell):
+    """the signed digits of cntt_gadget.h, d_1 first"""
+    s = w - beta * ell
+    state = x if s == 0 else ((x + (1 << (s - 1))) % (1 << w)) >> s
+    B, out = 1 << beta, []
+    for _ in range(ell):
+        d = state % B
+        state >>= beta
+        if d >= B // 2:
+            d -= B
+            state += 1
+        out.append(d)
+    return out[::-1]
+
+
+def model_keyswitch(lwe, ksk, lin, lout, stride, w, beta, ell):
+    """lwe: lin + 1 ints, ksk: flat ints with rows of `stride` words -> lout + 1 ints"""
+    M = 1 << w
+    out = [0] * lout + [lwe[lin]]
+    for i in range(lin):
+        for l, d in enumerate(digits(lwe[i], w, beta, ell)):
+            if d:
+                base = (i * ell + l) * stride
+                for c in range(lout + 1):
+                    out[c] = (out[c] - d * ksk[base + c]) % M
+    return out
+
+
+def rounded(x, w, beta, ell):
+    """r of cntt_gadget.h: the (beta * ell)-bit number closest to x / 2^s, ties up, wrapping at the top"""
+    s = w - beta * ell
+    return (x if s == 0 else ((x + (1 << (s - 1))) % (1 << w)) >> s) % (1 << (beta * ell))
+
+
+def rand_word(rng, w):
+    return int.from_bytes(rng.bytes(w // 8), "little")
+
+
+@pytest.mark.parametrize("w,beta,ell", [(32, 8, 4), (32, 5, 3), (64, 16, 4), (64, 4, 3), (64, 31, 2), (128, 16, 8), (128, 7, 5), (32, 1, 9)])
+def test_model_satisfies_the_phase_identity_of_the_header(w, beta, ell):
+    """With a noise-free key (row (i, l) = (a, <a, s_out> + s_in[i] 2^(w - beta l))) the phase of the model's output under the output key
+    is body - sum_i s_in[i] r_i 2^s exactly, r_i the rounded word and s = w - beta ell (s = 0 and s > 0 both among the cases)."""
+    M, s = 1 << w, w - beta * ell
+    rng = np.random.default_rng(w * 1000 + beta * 10 + ell)
+    lin, lout, stride = 9, 5, 8
+    s_in = [int(x) for x in rng.integers(0, 2, size=lin)]
+    s_out = [int(x) for x in rng.integers(0, 2, size=lout)]
+    ksk = [rand_word(rng, w) for _ in range(lin * ell * stride)]     # the padding words stay random
+    for i in range(lin):
+        for l in range(1, ell + 1):
+            base = (i * ell + l - 1) * stride
+            ksk[base + lout] = (sum(a * t for a, t in zip(ksk[base:base + lout], s_out)) + s_in[i] * (1 << (w - beta * l))) % M
+    edge = [0, M - 1, M - (1 << s >> 1), (M - (1 << s >> 1) - 1) % M, 1 << (w - 1), (1 << s >> 1)]
+    for trial in range(4):
+        lwe = [edge[(trial + i) % len(edge)] if i % 2 else rand_word(rng, w) for i in range(lin)] + [rand_word(rng, w)]
+        out = model_keyswitch(lwe, ksk, lin, lout, stride, w, beta, ell)
+        phase = (out[lout] - sum(a * t for a, t in zip(out, s_out))) % M
+        want = (lwe[lin] - sum(t * rounded(x, w, beta, ell) * (1 << s) for x, t in zip(lwe, s_in))) % M
+        assert phase == want, (w, beta, ell, trial)
+        for x in lwe[:lin]:                                           # the digits recompose to r
+            ds = digits(x, w, beta, ell)
+            assert all(-(1 << beta) // 2 <= d < (1 << beta) // 2 for d in ds)
+            assert sum(d << (beta * (ell - 1 - j)) for j, d in enumerate(ds)) % (1 << (beta * ell)) == rounded(x, w, beta, ell)
+
+
+# -- the surface -----------------------------------------------------------------------------------------------------------------
+def declarations(path):
+    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    return re.findall(r"\b(cntt_[a-z0-9_]+)\s*\([^;{}]*\)\s*;", text)
+
+
+def test_header_is_plain_c11_and_reached_through_cntt_ext_h():
+    for path in (KS, EXT):
+        r = subprocess.run(["gcc", "-std=c11", "-pedantic", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-x", "c", path],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+    assert set(declarations(KS)) == NEW and len(declarations(KS)) == 3
+    text = subprocess.run(["gcc", "-std=c11", "-E", "-P", "-x", "c", EXT], check=True, capture_output=True, text=True).stdout
+    assert NEW <= set(re.findall(r"\b(cntt_[a-z0-9_]+)\s*\(", text))
+    lines = open(EXT).read().splitlines()
+    assert lines.index('#include "cntt_keyswitch.h"') > lines.index('#include "cntt_pbs.h"')
+    assert "No keyswitch" not in open(PBS).read() and "cntt_keyswitch.h" in open(PBS).read()
+
+
+def test_library_exports_the_three_symbols():
+    cntt.lib()
+    so = os.path.join(ROOT, "concrete-ntt_amd", "libcntt_hip.so")
+    syms = subprocess.run(["nm", "-D", "--defined-only", so], check=True, capture_output=True, text=True).stdout
+    assert NEW <= set(re.findall(r"\b(cntt_[a-z0-9_]+)\b", syms))
+
+
+def test_existing_headers_keep_their_surface():
+    base = declarations(HEADER)
+    assert len(base) == 87, len(base)
+    assert sorted(declarations(EXT)) == ["cntt_native_external_product_batch", "cntt_native_max_terms"]
+    assert len(declarations(PBS)) == 5
+    for path in (HEADER, EXT, PBS):
+        assert not (NEW & set(re.findall(r"\b(cntt_[a-z0-9_]+)\s*\(", open(path).read()))), path
+
+
+def test_keyswitch_kernels_have_no_scratch_and_no_spills(tmp_path):
+    """The gfx950 code object of the new unit: one kernel, for u32 / u64 / 128-bit words, none with a private segment or a spilled
+    register."""
+    llvm = "/opt/rocm/lib/llvm/bin"
+    if not os.path.exists(os.path.join(llvm, "clang-offload-bundler")):
+        assert os.environ.get("CNTT_REQUIRE_CODE_OBJECTS") != "1", "ROCm LLVM tools not present"
+        pytest.skip("ROCm LLVM tools not present on this machine")
+    obj = os.path.join(ROOT, "concrete-ntt_amd", "csrc", "_obj", "native_keyswitch.o")
+    assert os.path.exists(obj), "objects not built in-tree (run __graft_entry__.build())"
+    fat, co = str(tmp_path / "ks.fat"), str(tmp_path / "ks.co")
+    subprocess.run([os.path.join(llvm, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
+    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                    "--input=" + fat, "--output=" + co, "--unbundle"], check=True)
+    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+    seen = []
+    for blk in notes.split("- .agpr_count")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        spills = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)) + int(re.search(r"\.sgpr_spill_count:\s+(\d+)", blk).group(1))
+        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1))
+        assert spills == 0 and scratch == 0, (name, spills, scratch)
+        seen.append(name)
+    assert len(seen) == 3 and all("native_keyswitch_kernel" in s for s in seen), seen
+
+
+@pytest.mark.parametrize("cls,wb", [(native32.Plan32, 4), (native64.Plan32, 8), (native128.Plan32, 16), (native64.Plan52, 8)])
+def test_workspace_bytes_is_the_formula_of_the_header(cls, wb):
+    def up(x):
+        return (x + 255) // 256 * 256
+
+    assert "cntt_native_pbs_workspace_bytes(plan, L, k, levels, batch) + up(batch * (L + 1) * wb)" in open(KS).read()
+    for n, L, k, levels, batch in ((32, 0, 1, 1, 1), (1024, 7, 1, 3, 5), (256, 630, 2, 4, 37), (2048, 3, 0, 2, 1000)):
+        plan = cls.try_new(n)
+        want = plan.pbs_workspace_bytes(L, k, levels, batch) + up(batch * (L + 1) * wb)
+        assert plan.ks_pbs_workspace_bytes(L, k, levels, batch) == want, (n, L, k, levels, batch)
+    assert cntt.lib().cntt_native_ks_pbs_workspace_bytes(None, 5, 1, 2, 3) == 0
+
+
+# -- CNTT_EINVAL: host buffers, refused before any device call ---------------------------------------------------------------------
+N, L, K, B = 32, 3, 1, 2
+LIN, LOUT, STRIDE = 6, 4, 6
+
+
+def ptr(a):
+    return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+
+def err():
+    return cntt.lib().cntt_last_error().decode()
+
+
+class Case:
+    """Valid host arguments of both calls for native64 Plan32 at n = 32: the keyswitch alone from 6 to 4 words with rows of 6, and
+    the combined call with L = 3, k = 1, batch = 2; outputs filled with 7."""
+
+    def __init__(self):
+        self.plan = native64.Plan32.try_new(N)
+        self.ks_levels, self.levels = 3, 2
+        self.lwe_in = np.arange(B * (LIN + 1), dtype=np.uint64)
+        self.lwe_out = np.full(B * (LOUT + 1), 7, dtype=np.uint64)
+        self.ksk = np.arange(LIN * self.ks_levels * STRIDE, dtype=np.uint64)
+        # the combined call
+        self.big_in = np.arange(B * (K * N + 1), dtype=np.uint64)
+        self.big_out = np.full(B * (K * N + 1), 7, dtype=np.uint64)
+        self.big_ksk = np.arange(K * N * self.ks_levels * (L + 1), dtype=np.uint64)
+        self.lut = np.arange((K + 1) * N, dtype=np.uint64)
+        self.keys = [np.zeros(L * (K + 1) * self.levels * (K + 1) * N, dtype=np.uint32) for _ in range(self.plan.NPRIMES)]
+        self.ws = np.zeros(self.plan.ks_pbs_workspace_bytes(L, K, self.levels, B), dtype=np.uint8)
+
+    def kp(self, null_plane=None):
+        return (ctypes.c_void_p * self.plan.NPRIMES)(*[None if i == null_plane else k.ctypes.data for i, k in enumerate(self.keys)])
+
+    def ks(self, base_log=8, levels=None, out="own", lwe_in="own", ksk="own", stride=STRIDE, lin=LIN, lout=LOUT, batch=B, plan="own"):
+        out = self.lwe_out if isinstance(out, str) else out
+        lwe_in = self.lwe_in if isinstance(lwe_in, str) else lwe_in
+        ksk = self.ksk if isinstance(ksk, str) else ksk
+        return cntt.lib().cntt_native_keyswitch_batch(self.plan._h if plan == "own" else plan, ptr(out), ptr(lwe_in), ptr(ksk), lin, lout,
+                                                      stride, base_log, self.ks_levels if levels is None else levels, batch, 0, None)
+
+    def both(self, ks_base_log=8, ks_levels=None, base_log=8, levels=None, out="own", lwe_in="own", ksk="own", lut="own", keys="own",
+             stride=L + 1, ws=None, ws_bytes=None, batch=B):
+        out = self.big_out if isinstance(out, str) else out
+        lwe_in = self.big_in if isinstance(lwe_in, str) else lwe_in
+        ksk = self.big_ksk if isinstance(ksk, str) else ksk
+        lut = self.lut if isinstance(lut, str) else lut
+        keys = self.kp() if isinstance(keys, str) else keys
+        return cntt.lib().cntt_native_keyswitch_bootstrap_batch(
+            self.plan._h, ptr(out), ptr(lwe_in), ptr(ksk), stride, ks_base_log, self.ks_levels if ks_levels is None else ks_levels,
+            ptr(lut), 0, keys, L, K, base_log, self.levels if levels is None else levels, batch, ptr(ws),
+            (0 if ws is None else ws.nbytes) if ws_bytes is None else ws_bytes, 0, None)
+
+    def untouched(self):
+        return (self.lwe_out == 7).all() and (self.big_out == 7).all()
+
+
+BAD = [(0, 2, "base_log is 0"), (8, 0, "levels is 0"), (33, 2, "base_log * "), (1, 65, "base_log * "), (32, 2, "base_log = 32 exceeds 31"), (32, 1, "base_log = 32 exceeds 31")]
+
+
+@pytest.mark.parametrize("base_log,levels,word", BAD)
+def test_the_digit_cases_are_refused(base_log, levels, word):
+    c = Case()
+    assert c.ks(base_log=base_log, levels=levels) == EINVAL and word in err()
+    assert c.both(ks_base_log=base_log, ks_levels=levels) == EINVAL and "ks_" + word in err()
+    assert c.untouched()
+
+
+def test_base_log_above_31_is_refused_for_every_word_width():
+    for cls in (native32.Plan32, native64.Plan32, native128.Plan32):
+        plan = cls.try_new(N)
+        c = Case()
+        assert c.ks(base_log=32, levels=1, plan=plan._h) == EINVAL and "base_log = 32 exceeds 31" in err()
+        assert c.untouched()
+    assert "31" in re.sub(r"\s+", " ", open(KS).read()).split("Valid:")[1][:200]   # the header states it
+
+
+def test_the_bootstrap_cases_of_the_combined_call_are_refused():
+    c = Case()
+    for base_log, levels, word in [(0, 2, "base_log is 0"), (8, 0, "levels is 0"), (33, 2, "base_log * levels")]:
+        assert c.both(base_log=base_log, levels=levels) == EINVAL and word in err() and "ks_" not in err()
+    assert c.both(keys=c.kp(null_plane=3)) == EINVAL and "key residue plane" in err()
+    assert c.both(keys=None) == EINVAL and "bsk_ntt" in err()
+    assert c.untouched()
+
+
+def test_row_stride_below_a_row_is_refused():
+    c = Case()
+    assert c.ks(stride=LOUT) == EINVAL and "row_stride" in err()
+    assert c.ks(stride=0) == EINVAL and "row_stride" in err()
+    assert c.both(stride=L) == EINVAL and "row_stride" in err()
+    assert c.untouched()
+
+
+def test_null_arguments_are_refused():
+    c = Case()
+    assert c.ks(plan=None) == EINVAL and "plan" in err()
+    assert c.ks(out=None) == EINVAL and "lwe_out" in err()
+    assert c.ks(lwe_in=None) == EINVAL and "lwe_in" in err()
+    assert c.ks(ksk=None) == EINVAL and "ksk" in err()
+    assert c.both(out=None) == EINVAL and "lwe_out" in err()
+    assert c.both(lwe_in=None) == EINVAL and "lwe_in" in err()
+    assert c.both(ksk=None) == EINVAL and "ksk" in err()
+    assert c.both(lut=None) == EINVAL and "lut" in err()
+    assert c.untouched()
+
+
+def test_overlaps_are_refused():
+    c = Case()
+    big = np.full(4096, 7, dtype=np.uint64)
+    out = big[:B * (LOUT + 1)]
+    assert c.ks(out=out, lwe_in=big[4:4 + B * (LIN + 1)]) == EINVAL and "lwe_out overlaps lwe_in" in err()
+    assert c.ks(out=out, ksk=big[9:9 + c.ksk.size]) == EINVAL and "lwe_out overlaps ksk" in err()
+    # the last row of a padded key ends after its LOUT + 1 words: an output right behind them does not overlap
+    rows = LIN * c.ks_levels
+    end = (rows - 1) * STRIDE + LOUT + 1
+    assert c.ks(out=big[end:end + B * (LOUT + 1)], ksk=big[:end]) != EINVAL
+    bout = big[:B * (K * N + 1)]
+    ws = big.view(np.uint8)[16 * 8:16 * 8 + c.ws.nbytes]
+    assert c.both(out=bout, lwe_in=big[8:8 + B * (K * N + 1)]) == EINVAL and "lwe_out overlaps lwe_in" in err()
+    assert c.both(out=bout, ksk=big[8:8 + c.big_ksk.size]) == EINVAL and "lwe_out overlaps ksk" in err()
+    assert c.both(out=bout, lut=big[8:8 + (K + 1) * N]) == EINVAL and "lwe_out overlaps lut" in err()
+    assert c.both(out=bout, ws=ws) == EINVAL and "lwe_out overlaps workspace" in err()
+    assert c.both(lwe_in=big[:B * (K * N + 1)], ws=ws) == EINVAL and "lwe_in overlaps workspace" in err()
+    assert c.both(ksk=big[:c.big_ksk.size], ws=ws) == EINVAL and "ksk overlaps workspace" in err()
+    assert c.both(lut=big[:(K + 1) * N], ws=ws) == EINVAL and "lut overlaps workspace" in err()
+    assert c.untouched()
+
+
+def test_workspace_too_small_or_misaligned_is_refused():
+    c = Case()
+    pbs_only = c.plan.pbs_workspace_bytes(L, K, c.levels, B)
+    assert c.both(ws=c.ws, ws_bytes=c.ws.nbytes - 1) == EINVAL and "workspace_bytes" in err()
+    assert c.both(ws=c.ws, ws_bytes=pbs_only) == EINVAL and "workspace_bytes" in err()      # enough for the bootstrap only
+    odd = np.zeros(c.ws.nbytes + 16, dtype=np.uint8)
+    off = (4 - odd.ctypes.data) % 16                                                        # an address that is 4 mod 16
+    assert c.both(ws=odd[off:off + c.ws.nbytes]) == EINVAL and "aligned" in err()
+    assert c.untouched()
+
+
+def test_batch_zero_does_nothing():
+    c = Case()
+    L_ = cntt.lib()
+    assert L_.cntt_native_keyswitch_batch(c.plan._h, None, None, None, LIN, LOUT, STRIDE, 8, 3, 0, 0, None) == 0
+    assert L_.cntt_native_keyswitch_bootstrap_batch(c.plan._h, None, None, None, L + 1, 8, 3, None, 0, None, L, K, 8, 2, 0, None, 0, 0,
+                                                    None) == 0
+
+
+def test_python_wrappers_panic_on_bad_shapes():
+    c = Case()
+    p = c.plan
+    with pytest.raises(cntt.Panic):
+        p.keyswitch_batch(c.lwe_out[:-1], c.lwe_in, c.ksk, LIN, LOUT, 8, 3, row_stride=STRIDE)          # lwe_out too short
+    with pytest.raises(cntt.Panic):
+        p.keyswitch_batch(c.lwe_out, c.lwe_in, c.ksk, LIN + 1, LOUT, 8, 3, row_stride=STRIDE)           # not whole ciphertexts
+    with pytest.raises(cntt.Panic):
+        p.keyswitch_batch(c.lwe_out, c.lwe_in, c.ksk[:-STRIDE], LIN, LOUT, 8, 3, row_stride=STRIDE)     # a key row missing
+    with pytest.raises(cntt.Panic):
+        p.keyswitch_batch(c.lwe_out, c.lwe_in, c.ksk, LIN, LOUT, 8, 3, row_stride=LOUT)                 # rows shorter than a ciphertext
+    with pytest.raises(cntt.Panic):
+        p.keyswitch_batch(c.lwe_out, c.lwe_in, c.ksk, LIN, LOUT, 8, 4, row_stride=STRIDE)               # key sized for levels = 3
+    with pytest.raises(cntt.Panic):
+        p.keyswitch_batch(c.lwe_out, c.lwe_in, c.ksk, LIN, LOUT, 0, 3, row_stride=STRIDE)
+    with pytest.raises(cntt.Panic):   # through the C checks
+        p.keyswitch_batch(c.lwe_out, c.lwe_in, c.ksk, LIN, LOUT, 32, 2, row_stride=STRIDE)
+    with pytest.raises(cntt.Panic):
+        p.keyswitch_bootstrap_batch(c.big_out[:-1], c.big_in, c.big_ksk, 8, 3, c.lut, c.keys, L, K, 8, 2)
+    with pytest.raises(cntt.Panic):
+        p.keyswitch_bootstrap_batch(c.big_out, c.big_in, c.big_ksk[:-1], 8, 3, c.lut, c.keys, L, K, 8, 2)
+    with pytest.raises(cntt.Panic):
+        p.keyswitch_bootstrap_batch(c.big_out, c.big_in, c.big_ksk, 8, 3, c.lut[:N], c.keys, L, K, 8, 2)
+    with pytest.raises(cntt.Panic):
+        p.keyswitch_bootstrap_batch(c.big_out, c.big_in, c.big_ksk, 8, 3, c.lut, c.keys[:-1], L, K, 8, 2)
+    with pytest.raises(cntt.Panic):   # through the C checks
+        p.keyswitch_bootstrap_batch(c.big_out, c.big_in, c.big_ksk, 33, 2, c.lut, c.keys, L, K, 8, 2)
+    with pytest.raises(cntt.Panic):
+        p.ks_pbs_workspace_bytes(L, K, 2, -1)
+    assert c.untouched()
