@@ -379,6 +379,42 @@ class NativePlan:
         check(lib().cntt_native_keyswitch_bootstrap_batch(self._h, op, ip, kp, row_stride, ks_base_log, ks_levels, lp, per, keys, lwe_dim,
                                                           glwe_dim, base_log, levels, batch, wp, wb, where, stream))
 
+    # -- LWE-to-GLWE packing keyswitch through the NTT (include/cntt_pack.h) --------------------------------------------------------------
+    def pack_workspace_bytes(self, lwe_dim_in, levels, batch):
+        """Bytes of workspace pack_keyswitch_batch needs: the negated digit polynomials of one chunk of mask words, rounded up to 256
+        bytes."""
+        if min(lwe_dim_in, batch) < 0 or levels <= 0:
+            raise Panic("lwe_dim_in and batch must not be negative, levels >= 1")
+        return lib().cntt_native_pack_workspace_bytes(self._h, lwe_dim_in, levels, batch)
+
+    def pack_keyswitch_batch(self, glwe_out, lwe_in, pksk_residues, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, workspace=None):
+        """glwe_out[g][p] = (sum_t lwe_in[g][t][lwe_dim_in] X^t if p == glwe_dim) - sum_{i,l} D_{g,i,l} (*) K[i*levels + l-1][p] mod 2^w,
+        D_{g,i,l}[t] = digit_l(lwe_in[g][t][i]) for t < lwe_count, else 0: lwe_count LWE ciphertexts packed into one GLWE ciphertext
+        whose coefficient t carries message t.  lwe_in: batch*lwe_count*(lwe_dim_in+1) words; glwe_out: batch*(glwe_dim+1)
+        polynomials; pksk_residues: NPRIMES buffers of lwe_dim_in*levels*(glwe_dim+1) residue polynomials as fwd_batch writes them for
+        the key polynomials, row (i, l) a GLWE encryption under the output key of the constant s_in[i] * 2^(w - base_log*l);
+        workspace: None (one allocation per call) or a buffer of pack_workspace_bytes()."""
+        ip, ic, where, stream = self._words(lwe_in)
+        op, oc, ow, _ = self._words(glwe_out)
+        n = self._n
+        if lwe_dim_in < 0 or glwe_dim < 0 or lwe_count <= 0 or levels <= 0 or base_log <= 0 or ic % (lwe_count * (lwe_dim_in + 1)) or ow != where:
+            raise Panic("lwe_in: batch*lwe_count*(lwe_dim_in+1) words; glwe_out in the same memory; lwe_count, base_log, levels >= 1")
+        batch = ic // (lwe_count * (lwe_dim_in + 1))
+        if oc != batch * (glwe_dim + 1) * n:
+            raise Panic("glwe_out must hold batch*(glwe_dim+1) = %d polynomials" % (batch * (glwe_dim + 1)))
+        if len(pksk_residues) != self.NPRIMES:
+            raise Panic("expected %d key residue buffers" % self.NPRIMES)
+        ptrs = []
+        for r in pksk_residues:
+            ptr, c, esz, w, _ = buffer_info(r)
+            if esz != self.RES or w != where or c != lwe_dim_in * levels * (glwe_dim + 1) * n:
+                raise Panic("key residue buffers: lwe_dim_in*levels*(glwe_dim+1) residue polynomials in the memory of the other buffers")
+            ptrs.append(ptr)
+        keys = (ctypes.c_void_p * self.NPRIMES)(*ptrs)
+        wp, wb = self._workspace(workspace, where)
+        check(lib().cntt_native_pack_keyswitch_batch(self._h, op, ip, keys, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, wp, wb,
+                                                     where, stream))
+
 
 def _make(kind, nprimes, word, res, binary, doc):
     return type("Plan", (NativePlan,), {"KIND": kind, "NPRIMES": nprimes, "WORD": word, "RES": res,

@@ -1,11 +1,13 @@
 // libcntt_hip.so host side, what is built on the native plans without a counterpart in the reference: the external product
 // (include/cntt_ext.h), rotation / gadget decomposition and the external product on undecomposed polynomials (include/cntt_gadget.h),
-// the programmable bootstrap (include/cntt_pbs.h), the LWE keyswitch and keyswitch + bootstrap (include/cntt_keyswitch.h).
+// the programmable bootstrap (include/cntt_pbs.h), the LWE keyswitch and keyswitch + bootstrap (include/cntt_keyswitch.h), the
+// LWE-to-GLWE packing keyswitch (include/cntt_pack.h).
 #include <cstdio>
 
 #include "host_common.hpp"
 #include "native_gadget.hpp"
 #include "native_keyswitch.hpp"
+#include "native_pack.hpp"
 #include "native_pbs.hpp"
 
 // ---------------------------------------------------------------------------------------------
@@ -626,5 +628,89 @@ extern "C" int cntt_native_keyswitch_bootstrap_batch(const cntt_native_t *pl, vo
     void *dout = s.out(lwe_out, eb), *dws = s.alloc(need);
     if (int rc = s.status()) return rc;
     if (int rc = run(dout, din, dk, dlut, dkey, static_cast<char *>(dws))) return rc;
+    return s.finish();
+}
+
+// ---------------------------------------------------------------------------------------------
+// LWE-to-GLWE packing keyswitch through the NTT (include/cntt_pack.h, native_pack.hpp)
+// ---------------------------------------------------------------------------------------------
+// mask words of one external product: C of the header, capped at lin (levels >= 1)
+static size_t pack_chunk(const cntt_native *pl, size_t lin, unsigned levels) {
+    const size_t c = std::max<size_t>(1, std::min<size_t>(pl->max_terms, CNTT_PACK_TERMS) / levels);
+    return std::min(c, lin);
+}
+static size_t pack_terms_bytes(const cntt_native *pl, size_t lin, unsigned levels, size_t batch) {
+    return batch * pack_chunk(pl, lin, levels) * levels * pl->n * (size_t)pl->info.word;
+}
+extern "C" size_t cntt_native_pack_workspace_bytes(const cntt_native_t *pl, size_t lwe_dim_in, unsigned levels, size_t batch) {
+    return pl && levels ? up256(pack_terms_bytes(pl, lwe_dim_in, levels, batch)) : 0;
+}
+
+// out = the body polynomial, then per chunk of mask words the negated digit polynomials into `terms` and the external product
+// accumulating into out.  In place is sound as in native_blind_rotate_device: a chunk's terms are complete before its product starts
+// and rewritten only after it (stream order), and the product reads only the terms and the key.
+static int native_pack_device(const cntt_native *pl, void *out, const void *in, const void *const *pksk, size_t lin, size_t m, size_t glwe_dim,
+                              unsigned base_log, unsigned levels, size_t batch, void *terms, hipStream_t st) {
+    const size_t npolys = glwe_dim + 1, n = pl->n, chunk = pack_chunk(pl, lin, levels);
+    const int logn = native_logn(pl);
+    hipError_t e = launch_native_pack_body(pl->info.word, out, in, logn, glwe_dim, lin, m, batch, ew_grid(batch * npolys * n), st);
+    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_pack_body_kernel launch failed: %s", hipGetErrorString(e));
+    const u128 off = gadget_offset(8u * (unsigned)pl->info.word, base_log, levels);
+    const size_t row = levels * npolys * n * pl->rbytes();   // one mask word's key rows, bytes per plane
+    const int k = pl->info.nprimes;
+    const void *key[10];
+    for (size_t i0 = 0; i0 < lin; i0 += chunk) {
+        const size_t nw = std::min(chunk, lin - i0);
+        for (int j = 0; j < k; ++j) key[j] = static_cast<const char *>(pksk[j]) + i0 * row;
+        e = launch_native_pack_decompose(pl->info.word, terms, in, (uint64_t)off, (uint64_t)(off >> 64), base_log, levels, logn, lin, m, i0, nw,
+                                         batch, st);
+        if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_pack_decompose_kernel launch failed: %s", hipGetErrorString(e));
+        if (int rc = native_ext_device(pl, out, terms, key, nw * levels, npolys, batch, true, st)) return rc;
+    }
+    return CNTT_OK;
+}
+
+extern "C" int cntt_native_pack_keyswitch_batch(const cntt_native_t *pl, void *glwe_out, const void *lwe_in, const void *const *pksk_ntt,
+                                                size_t lwe_dim_in, size_t lwe_count, size_t glwe_dim, unsigned base_log, unsigned levels,
+                                                size_t batch, void *workspace, size_t workspace_bytes, cntt_mem_t where, void *stream) {
+    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+    if (int rc = gadget_check(pl, base_log, levels, CNTT_SRC_PLAIN, nullptr)) return rc;
+    if (levels > pl->max_terms)
+        return fail(CNTT_EINVAL, "levels = %u exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range", levels,
+                    pl->max_terms);
+    if (lwe_count == 0 || lwe_count > pl->n)
+        return fail(CNTT_EINVAL, "lwe_count = %zu is not in 1 .. ntt_size = %zu", lwe_count, pl->n);
+    if (glwe_dim + 1 >= ((size_t)1 << 32)) return fail(CNTT_EINVAL, "glwe_dim too large");
+    if (batch == 0) return CNTT_OK;
+    if (!glwe_out) return fail(CNTT_EINVAL, "glwe_out is NULL");
+    if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
+    if (lwe_dim_in) {
+        if (!pksk_ntt) return fail(CNTT_EINVAL, "pksk_ntt is NULL");
+        if (int rc = check_key_planes(pl, pksk_ntt, "pksk_ntt")) return rc;
+    }
+    const size_t n = pl->n, w = (size_t)pl->info.word, ob = batch * (glwe_dim + 1) * n * w, ib = batch * lwe_count * (lwe_dim_in + 1) * w;
+    const size_t need = up256(pack_terms_bytes(pl, lwe_dim_in, levels, batch));
+    if (ranges_overlap(glwe_out, ob, lwe_in, ib)) return fail(CNTT_EINVAL, "glwe_out overlaps lwe_in");
+    if (workspace) {
+        if ((uintptr_t)workspace % 16) return fail(CNTT_EINVAL, "workspace is not 16-byte aligned");
+        if (workspace_bytes < need) return fail(CNTT_EINVAL, "workspace_bytes = %zu is below the %zu bytes this call needs", workspace_bytes, need);
+        if (ranges_overlap(glwe_out, ob, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "glwe_out overlaps workspace");
+        if (ranges_overlap(lwe_in, ib, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_in overlaps workspace");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (where == CNTT_MEM_DEVICE) {
+        void *terms = workspace;
+        if (!terms && lwe_dim_in) HIP_TRY(hipMallocAsync(&terms, need, st));   // one allocation for the whole call
+        const int rc = native_pack_device(pl, glwe_out, lwe_in, pksk_ntt, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, terms, st);
+        if (!workspace && terms) (void)hipFreeAsync(terms, st);
+        return rc;
+    }
+    Staging s(st);
+    const void *dkey[10];
+    if (lwe_dim_in) key_planes_to_device(pl, s, pksk_ntt, lwe_dim_in * levels * (glwe_dim + 1) * n * pl->rbytes(), dkey);
+    const void *din = s.in(lwe_in, ib);
+    void *dout = s.out(glwe_out, ob), *dterms = s.alloc(need);
+    if (int rc = s.status()) return rc;
+    if (int rc = native_pack_device(pl, dout, din, dkey, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, dterms, st)) return rc;
     return s.finish();
 }

@@ -254,6 +254,16 @@ template <cntt_native_kind_t KIND, class R, int NPRIMES, int WORD_BYTES> class N
                                                     lut_per_element ? 1 : 0, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace,
                                                     workspace_bytes, where, stream));
     }
+    // LWE-to-GLWE packing keyswitch through the NTT (cntt_pack.h): lwe_count LWE ciphertexts of dimension lwe_dim_in into one GLWE
+    size_t pack_workspace_bytes(size_t lwe_dim_in, unsigned levels, size_t batch) const {
+        return cntt_native_pack_workspace_bytes(h_, lwe_dim_in, levels, batch);
+    }
+    void pack_keyswitch_batch(void *glwe_out, const void *lwe_in, const void *const *pksk_ntt, size_t lwe_dim_in, size_t lwe_count,
+                              size_t glwe_dim, unsigned base_log, unsigned levels, size_t batch, void *workspace = nullptr,
+                              size_t workspace_bytes = 0, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(cntt_native_pack_keyswitch_batch(h_, glwe_out, lwe_in, pksk_ntt, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch,
+                                               workspace, workspace_bytes, where, stream));
+    }
 };
 }  // namespace detail
 

@@ -63,4 +63,7 @@ size_t cntt_native_max_terms(const cntt_native_t *plan);
  * that chains with itself, likewise. */
 #include "cntt_keyswitch.h"
 
+/* The packing keyswitch that takes LWE ciphertexts back into one GLWE ciphertext, through the NTT, likewise. */
+#include "cntt_pack.h"
+
 #endif /* CNTT_EXT_H */
