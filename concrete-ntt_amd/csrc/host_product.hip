@@ -133,7 +133,8 @@ static hipError_t product_fused2_try(const cntt_product *pl, bool inv, uint64_t 
     // 8 % faster than the fused forward kernel (N = 2048, 32768 polynomials: 0.497 vs 0.542 ms) -- the fused one reads its
     // twiddles from L2 at three wavefronts per SIMD, the batched transforms from an LDS image -- while the fused inverse
     // (two transforms + Garner, no residue round trip) still wins (Replace 0.445 vs 0.522 ms; Accumulate 0.599 vs 0.582: a
-    // tie).  cntt_debug_set("product_fused", 0 / 1) forces neither / both for A/B timing; results are identical (tests/test_product.py).
+    // tie).  cntt_debug_set("product_fused", 0 / 1) forces neither / both for A/B timing; results are identical
+    // (tests/test_gpu_switch_settings.py: test_gpu_product_fused_settings runs every call under -1, 0 and 1 against the oracle).
     const int force = debug_switch(DBG_PRODUCT_FUSED);
     if (force == 0 || (force < 0 && !inv)) return hipErrorNotSupported;
     const cntt_plan32 *q0 = pl->p32[0].get(), *q1 = pl->p32[1].get();

@@ -2,8 +2,10 @@
 fwd / mul_accumulate / inv called in sequence (src/prime64.rs:794, :1085-1128, :872).  Covers the fused kernels (persistent
 walk with an LDS twiddle image up to n = 2048 u64 / 4096 u32, wave-block walk for u64 n = 4096 ... 16384, one element per
 workgroup for u32 n = 8192 ... 32768; nout <= 4 -- three / four outputs of the largest size of each width as two launches
-of <= 2 outputs), the composed path (single-pass sizes, nout = 5, the Montgomery class at large n), every arithmetic class,
-ragged batches, accumulate mode and the empty sum.  Bit-exact."""
+of <= 2 outputs in the classes where that measured faster: u64 p < 2^51 and 2^64 - c, u32 p < 2^30), the composed path
+(single-pass sizes, nout = 5, the Montgomery class at large n, and three / four outputs of the largest size in the other
+classes: u64 62- / 63-bit, u32 31-bit and p >= 2^31), every arithmetic class, ragged batches, accumulate mode and the empty
+sum.  Bit-exact.  (tests/test_gpu_switch_settings.py runs the split and the composed form of every class.)"""
 import numpy as np
 import pytest
 
@@ -60,9 +62,9 @@ CASES = [
     (32, 16384, P32, 2, 3, 2),       # p >= 2^31 on doubles
     (32, 32768, P30, 2, 2, 2),
     (32, 32768, P32, 2, 1, 1),       # p >= 2^31 at this size (Montgomery class until round 3, doubles since)
-    (32, 32768, P30, 2, 3, 1),       # ... three / four outputs at n = 32768: two fused launches of <= 2 outputs (round 4)
+    (32, 32768, P30, 2, 3, 1),       # ... three / four outputs at n = 32768, 30-bit class: two fused launches of <= 2 outputs (round 4)
     (32, 32768, P30, 3, 4, 2),
-    (32, 32768, P32, 2, 3, 1),       # p >= 2^31 at this size: on doubles since round 4
+    (32, 32768, P32, 2, 3, 1),       # p >= 2^31 at this size (on doubles since round 4): three outputs run the composed path by default
     # the chain on the wave-block walk (ExtBlk): u64 n = 4096 / 8192 (1 .. 4 outputs) and 16384 (1 .. 2), every class but the Montgomery one
     (64, 4096, P62, 3, 2, 3),
     (64, 4096, P62, 2, 1, 2),
@@ -79,10 +81,10 @@ CASES = [
     (64, 16384, 1125899904679937, 9, 2, 2),     # CLS_FP: more terms than the accumulator's reduction period
     (64, 16384, SOLINAS, 2, 2, 1),
     (64, 16384, P63, 2, 1, 2),
-    (64, 16384, P62, 2, 3, 1),                  # ... three / four outputs: two fused launches of <= 2 outputs (round 4)
-    (64, 16384, P62, 3, 4, 2),
-    (64, 16384, 1125899904679937, 9, 4, 1),     # CLS_FP, split launches, more terms than the accumulator's reduction period
-    (64, 16384, SOLINAS, 2, 3, 2),
+    (64, 16384, P62, 2, 3, 1),                  # ... three / four outputs: the composed path by default in the 62- / 63-bit classes
+    (64, 16384, P62, 3, 4, 2),                  #     (the split launches measured slower there: csrc/host_prime.hip, ext_split_wins)
+    (64, 16384, 1125899904679937, 9, 4, 1),     # CLS_FP: two fused launches of <= 2 outputs by default; more terms than the accumulator's reduction period
+    (64, 16384, SOLINAS, 2, 3, 2),              # 2^64 - c: split launches by default too
     (64, 16384, 9224497936763846657, 2, 3, 1),  # Montgomery class at this size: no fused kernel at all, composed path
     # three / four 64-bit accumulator tiles: the shapes that run without the next-term prefetch (ExtWp NEXT = false) ...
     (64, 2048, P62, 3, 3, 3),

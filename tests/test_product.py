@@ -118,6 +118,29 @@ def test_host_product_try_new(oracle, gp):
     assert pl is not None and pl.ntt_domain_len() == 0
 
 
+def test_host_product_try_new_five_to_seven_primes(oracle):
+    """More primes than any golden case: the host side of the plans tests/test_gpu_product_shapes.py runs on the GPU.  Seven
+    distinct primes = 1 mod 64 is the most a u64 modulus holds (with the eighth smallest, 1217, the product is past 2^64)."""
+    from concrete_ntt_amd import product
+    small = [193, 257, 449, 577, 641, 769, 1153]
+    for k in (5, 6, 7):
+        primes, big = small[:k], 1
+        for p in primes:
+            big *= p
+        assert big < 2**64
+        pl = product.Plan.try_new(32, big, primes[::-1])          # any order: try_new sorts
+        opl = oracle.Product.try_new(32, big, primes[::-1])
+        assert pl is not None and opl is not None, k
+        assert pl.primes() == primes and (len(pl.plan_32()), len(pl.plan_64())) == (k, 0)
+        assert pl.ntt_domain_len() == opl.ntt_domain_len() == 16 * k
+        inv = pl.modular_inverses()
+        assert inv.size == k * (k - 1) // 2 and np.array_equal(inv, opl.modular_inverses())
+        # the reference's order (src/product.rs:207-229): for each j, prime[i]^-1 mod prime[j] for i < j
+        assert [int(x) for x in inv] == [pow(primes[i], -1, primes[j]) for j in range(k) for i in range(j)]
+    # big is now the product of all seven; the next prime = 1 mod 64 takes it past a u64 word, so no modulus exists for eight
+    assert oracle.largest_prime_in_arithmetic_progression64(64, 1, 1154, 1217) == 1217 and big * 1217 >= 2**64
+
+
 def test_product_modes_api():
     from concrete_ntt_amd import product
     assert repr(product.FwdMode.Generic) == "Generic" and repr(product.FwdMode.Bounded(7)) == "Bounded(7)"
