@@ -77,6 +77,15 @@ def lib():
             "mul_accumulate_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_int, c_vp]),
             "mul_ntt_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_int, c_vp]),
             "external_product_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, c_int, c_int, c_vp]),
+            # include/cntt_prime_pbs.h
+            "gadget_decompose_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, ctypes.c_uint, c_int, c_sz, c_int, c_vp]),
+            "lwe_modswitch_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_int, c_vp]),
+            "blind_rotate_batch": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz,
+                                           c_int, c_vp]),
+            "sample_extract_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, c_int, c_vp]),
+            "bootstrap_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz,
+                                        c_int, c_vp]),
+            "pbs_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, c_sz]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, p + name)

@@ -559,3 +559,6 @@ template int pointwise_device<uint32_t, PW_MUL_ACCUMULATE>(const PrimePlan<uint3
 template int pointwise_device<uint64_t, PW_MUL_ACCUMULATE>(const PrimePlan<uint64_t> *, uint64_t *, const uint64_t *, const uint64_t *, size_t, hipStream_t);
 template int external_product_device<uint32_t>(const PrimePlan<uint32_t> *, uint32_t *, const uint32_t *, const uint32_t *, size_t, size_t, size_t, bool, hipStream_t);
 template int external_product_device<uint64_t>(const PrimePlan<uint64_t> *, uint64_t *, const uint64_t *, const uint64_t *, size_t, size_t, size_t, bool, hipStream_t);
+
+// the programmable bootstrap mod p around external_product_device (include/cntt_prime_pbs.h)
+#include "host_prime_pbs.inc"

@@ -22,6 +22,7 @@
 
 #include "cntt.h"
 #include "cntt_ext.h"
+#include "cntt_prime_pbs.h"
 
 namespace cntt {
 
@@ -83,6 +84,28 @@ template <class T> struct PrimeApi;
                                           size_t k, int acc, cntt_mem_t w, void *s) {                                 \
             return cntt_prime##BITS##_external_product_batch(h, o, t, key, j, no, k, acc, w, s);                      \
         }                                                                                                            \
+        /* cntt_prime_pbs.h */                                                                                       \
+        static int gadget_decompose_batch(const handle *h, T *t, const T *f, const uint32_t *rot, size_t np, unsigned bl,       \
+                                          unsigned lv, cntt_src_mode_t m, size_t k, cntt_mem_t w, void *s) {         \
+            return cntt_prime##BITS##_gadget_decompose_batch(h, t, f, rot, np, bl, lv, m, k, w, s);                   \
+        }                                                                                                            \
+        static int lwe_modswitch_batch(const handle *h, uint32_t *r, const T *lwe, size_t ld, size_t k, cntt_mem_t w, void *s) { \
+            return cntt_prime##BITS##_lwe_modswitch_batch(h, r, lwe, ld, k, w, s);                                    \
+        }                                                                                                            \
+        static int blind_rotate_batch(const handle *h, T *acc, const T *lut, int per, const uint32_t *r, const T *bsk, size_t ld,  \
+                                      size_t gd, unsigned bl, unsigned lv, size_t k, void *ws, size_t wsb, cntt_mem_t w, void *s) { \
+            return cntt_prime##BITS##_blind_rotate_batch(h, acc, lut, per, r, bsk, ld, gd, bl, lv, k, ws, wsb, w, s); \
+        }                                                                                                            \
+        static int sample_extract_batch(const handle *h, T *o, const T *g, size_t gd, size_t idx, size_t k, cntt_mem_t w, void *s) { \
+            return cntt_prime##BITS##_sample_extract_batch(h, o, g, gd, idx, k, w, s);                                \
+        }                                                                                                            \
+        static int bootstrap_batch(const handle *h, T *o, const T *in, const T *lut, int per, const T *bsk, size_t ld, size_t gd,  \
+                                   unsigned bl, unsigned lv, size_t k, void *ws, size_t wsb, cntt_mem_t w, void *s) {  \
+            return cntt_prime##BITS##_bootstrap_batch(h, o, in, lut, per, bsk, ld, gd, bl, lv, k, ws, wsb, w, s);     \
+        }                                                                                                            \
+        static size_t pbs_workspace_bytes(const handle *h, size_t ld, size_t gd, unsigned lv, size_t k) {             \
+            return cntt_prime##BITS##_pbs_workspace_bytes(h, ld, gd, lv, k);                                          \
+        }                                                                                                            \
     };
 CNTT_PRIME_TRAITS(32, uint32_t)
 CNTT_PRIME_TRAITS(64, uint64_t)
@@ -141,6 +164,35 @@ template <class T> class PrimePlan {
     void external_product_batch(T *out, const T *terms, const T *key_ntt, size_t nterms, size_t nout, size_t batch,
                                 bool accumulate = false, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
         check(A::external_product_batch(h_, out, terms, key_ntt, nterms, nout, batch, accumulate ? 1 : 0, where, stream));
+    }
+    // programmable bootstrap mod p (cntt_prime_pbs.h): signed digits of the balanced lift of polys, X^rot polys or X^rot polys - polys;
+    // modulus switch to exponents below 2n; blind rotation in place over bsk_ntt = n^-1 fwd(key); sample extraction; all in one call
+    void gadget_decompose_batch(T *terms, const T *polys, const uint32_t *rot, size_t npolys, unsigned base_log, unsigned levels,
+                                cntt_src_mode_t src_mode, size_t batch, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(A::gadget_decompose_batch(h_, terms, polys, rot, npolys, base_log, levels, src_mode, batch, where, stream));
+    }
+    void lwe_modswitch_batch(uint32_t *rot_t, const T *lwe, size_t lwe_dim, size_t batch, cntt_mem_t where = CNTT_MEM_DEVICE,
+                             void *stream = nullptr) const {
+        check(A::lwe_modswitch_batch(h_, rot_t, lwe, lwe_dim, batch, where, stream));
+    }
+    void blind_rotate_batch(T *acc, const T *lut, bool lut_per_element, const uint32_t *rot_t, const T *bsk_ntt, size_t lwe_dim,
+                            size_t glwe_dim, unsigned base_log, unsigned levels, size_t batch, void *workspace = nullptr,
+                            size_t workspace_bytes = 0, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(A::blind_rotate_batch(h_, acc, lut, lut_per_element ? 1 : 0, rot_t, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch,
+                                    workspace, workspace_bytes, where, stream));
+    }
+    void sample_extract_batch(T *lwe_out, const T *glwe, size_t glwe_dim, size_t index, size_t batch, cntt_mem_t where = CNTT_MEM_DEVICE,
+                              void *stream = nullptr) const {
+        check(A::sample_extract_batch(h_, lwe_out, glwe, glwe_dim, index, batch, where, stream));
+    }
+    void bootstrap_batch(T *lwe_out, const T *lwe_in, const T *lut, bool lut_per_element, const T *bsk_ntt, size_t lwe_dim,
+                         size_t glwe_dim, unsigned base_log, unsigned levels, size_t batch, void *workspace = nullptr,
+                         size_t workspace_bytes = 0, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(A::bootstrap_batch(h_, lwe_out, lwe_in, lut, lut_per_element ? 1 : 0, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch,
+                                 workspace, workspace_bytes, where, stream));
+    }
+    size_t pbs_workspace_bytes(size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) const {
+        return A::pbs_workspace_bytes(h_, lwe_dim, glwe_dim, levels, batch);
     }
     const typename A::handle *handle() const { return h_; }
 };
