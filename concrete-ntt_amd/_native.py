@@ -5,11 +5,12 @@ import numpy as np
 
 from . import _lib
 from ._lib import Panic, buffer_info, check, lib
+from ._pbs import PbsMixin
 from .prime32 import Plan as _Plan32
 from .prime64 import Plan as _Plan64
 
 
-class NativePlan:
+class NativePlan(PbsMixin):
     """Mirrors the reference's PlanNN types: try_new(n), ntt_size(), ntt_i(), fwd, fwd_binary, inv,
     negacyclic_polymul (e.g. src/native64.rs:930-1070).  Coefficients: numpy uint32 / uint64 arrays;
     u128 words are (lo, hi) uint64 pairs, i.e. arrays of 2n uint64 (16-byte little-endian)."""
@@ -161,42 +162,7 @@ class NativePlan:
         check(lib().cntt_native_external_product_batch(self._h, op, tp, keys, nterms, nout, batch, 1 if accumulate else 0, where,
                                                        stream))
 
-    # -- rotation / CMux difference / signed gadget decomposition (include/cntt_gadget.h) ----------------------------------------
-    SRC_MODES = {"plain": 0, "rotate": 1, "cmux": 2}
-
-    def _src(self, polys, rot, mode):
-        """(polys pointer, word count, memory, stream, rot pointer, mode number) with the shape checks the two calls share."""
-        if mode not in self.SRC_MODES:
-            raise Panic("mode must be one of %s" % sorted(self.SRC_MODES))
-        pp, pc, where, stream = self._words(polys)
-        rp = None
-        if rot is not None:
-            rp, rc_, esz, rw, _ = buffer_info(rot)
-            if esz != 4 or rw != where:
-                raise Panic("rot: one uint32 exponent per batch element, in the memory of polys")
-            rp = (rp, rc_)
-        elif mode != "plain":
-            raise Panic("mode %r needs rot" % mode)
-        return pp, pc, where, stream, rp, self.SRC_MODES[mode]
-
-    def gadget_decompose_batch(self, terms, polys, base_log, levels, rot=None, mode="plain"):
-        """terms[b][p*levels + l-1] = signed digit l (of `levels`, base_log bits each, d_1 most significant) of the source polynomial
-        of polys[b][p]: polys itself ("plain"), X^rot[b] * polys ("rotate") or X^rot[b] * polys - polys ("cmux") in Z/2^w[X]/(X^n+1).
-        polys: batch*npolys polynomials; terms: batch*npolys*levels; npolys is taken from len(rot) = batch when rot is given, else 1."""
-        pp, pc, where, stream, rp, m = self._src(polys, rot, mode)
-        tp, tc, tw, _ = self._words(terms)
-        n = self._n
-        if levels <= 0 or base_log <= 0 or pc % n or tw != where or tc != pc * levels:
-            raise Panic("polys: batch*npolys polynomials; terms: levels times as many in the same memory; base_log, levels >= 1")
-        batch = rp[1] if rp else pc // n
-        if batch == 0 or (pc // n) % batch:
-            if pc:
-                raise Panic("polys must hold a whole number of polynomials per exponent in rot")
-            batch = 0
-        npolys = (pc // n) // batch if batch else 0
-        check(lib().cntt_native_gadget_decompose_batch(self._h, tp, pp, rp[0] if rp else None, npolys, base_log, levels, m, batch,
-                                                       where, stream))
-
+    # -- rotation / CMux difference / signed gadget decomposition (include/cntt_gadget.h): gadget_decompose_batch is PbsMixin's -----------
     def external_product_decomposed_batch(self, out, polys, key_residues, base_log, levels, nout, rot=None, mode="plain",
                                           addend=None):
         """out[b][o] = (addend[b][o] if addend is given) + sum_{p,l} digit_l(source(polys[b][p])) (*) key[p*levels + l-1][o] mod 2^w:
@@ -229,21 +195,10 @@ class NativePlan:
         check(lib().cntt_native_external_product_decomposed_batch(self._h, op, pp, rp[0] if rp else None, ap, keys, npolys, base_log,
                                                                   levels, m, nout, batch, where, stream))
 
-    # -- programmable bootstrap (include/cntt_pbs.h): modulus switch, blind rotation in place, sample extraction -------------------
-    def pbs_workspace_bytes(self, lwe_dim, glwe_dim, levels, batch):
-        """Bytes of workspace bootstrap_batch needs (digits + rot_t + accumulator, each 256-byte aligned); enough for
-        blind_rotate_batch too."""
-        if min(lwe_dim, glwe_dim, levels, batch) < 0:
-            raise Panic("lwe_dim, glwe_dim, levels and batch must not be negative")
-        return lib().cntt_native_pbs_workspace_bytes(self._h, lwe_dim, glwe_dim, levels, batch)
-
-    def _workspace(self, workspace, where):
-        if workspace is None:
-            return None, 0
-        ptr, count, esz, w, _ = buffer_info(workspace)
-        if w != where:
-            raise Panic("workspace must live in the memory of the other buffers")
-        return ptr, count * esz
+    # -- programmable bootstrap (include/cntt_pbs.h): modulus switch, blind rotation in place, sample extraction; the calls themselves:
+    #    PbsMixin ------------------------------------------------------------------------------------------------------------------------
+    def _fn(self, name):
+        return getattr(lib(), "cntt_native_" + name)
 
     def _bsk(self, bsk_residues, where, lwe_dim, glwe_dim, levels):
         if len(bsk_residues) != self.NPRIMES:
@@ -258,73 +213,21 @@ class NativePlan:
             ptrs.append(ptr)
         return (ctypes.c_void_p * self.NPRIMES)(*ptrs)
 
-    def _lut(self, lut, lut_per_element, where, glwe_dim, batch):
-        lp, lc, lw, _ = self._words(lut)
-        shared, each = (glwe_dim + 1) * self._n, batch * (glwe_dim + 1) * self._n
-        if lut_per_element is None:
-            lut_per_element = lc == each and lc != shared
-        if lw != where or lc != (each if lut_per_element else shared):
-            raise Panic("lut: glwe_dim+1 polynomials shared by the batch, or batch*(glwe_dim+1) with lut_per_element, in the memory "
-                        "of the other buffers")
-        return lp, 1 if lut_per_element else 0
-
-    def lwe_modswitch_batch(self, rot_t, lwe, lwe_dim):
-        """rot_t[i*batch + b] = round(lwe[b][i] * 2n / 2^w) mod 2n (ties up) for the lwe_dim mask words, and 2n minus that for the
-        body in row lwe_dim.  lwe: batch*(lwe_dim+1) words; rot_t: (lwe_dim+1)*batch uint32, transposed: row i is iteration i's rot."""
-        lp, lc, where, stream = self._words(lwe)
-        rp, rc_, esz, rw, _ = buffer_info(rot_t)
-        if lwe_dim < 0 or lc % (lwe_dim + 1) or esz != 4 or rw != where or rc_ != lc:
-            raise Panic("lwe: batch*(lwe_dim+1) words; rot_t: as many uint32 in the same memory")
-        check(lib().cntt_native_lwe_modswitch_batch(self._h, rp, lp, lwe_dim, lc // (lwe_dim + 1), where, stream))
-
     def blind_rotate_batch(self, acc, lut, rot_t, bsk_residues, lwe_dim, glwe_dim, base_log, levels, workspace=None,
                            lut_per_element=None):
-        """acc[b] = X^rot_t[lwe_dim][b] * lut, then for i < lwe_dim: acc[b] += ExtProd(bsk_i, X^rot_t[i][b] acc[b] - acc[b]), in place:
-        the words of gadget_decompose_batch(mode="cmux") + external_product_batch(accumulate=True) per iteration.  acc: batch*(glwe_dim+1)
-        polynomials (written only); lut: glwe_dim+1 polynomials, or batch*(glwe_dim+1) (lut_per_element; None: told by the size);
-        rot_t: (lwe_dim+1)*batch uint32 as lwe_modswitch_batch writes them; bsk_residues: NPRIMES buffers of
-        lwe_dim*(glwe_dim+1)*levels*(glwe_dim+1) residue polynomials; workspace: None (one allocation per call) or a buffer of
-        pbs_workspace_bytes()."""
-        ap, ac, where, stream = self._words(acc)
-        n = self._n
-        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or ac % ((glwe_dim + 1) * n):
-            raise Panic("acc: batch*(glwe_dim+1) polynomials; base_log, levels >= 1")
-        batch = ac // ((glwe_dim + 1) * n)
-        rp, rc_, esz, rw, _ = buffer_info(rot_t)
-        if esz != 4 or rw != where or rc_ != (lwe_dim + 1) * batch:
-            raise Panic("rot_t: (lwe_dim+1)*batch uint32 in the memory of acc")
-        lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
-        keys = self._bsk(bsk_residues, where, lwe_dim, glwe_dim, levels)
-        wp, wb = self._workspace(workspace, where)
-        check(lib().cntt_native_blind_rotate_batch(self._h, ap, lp, per, rp, keys, lwe_dim, glwe_dim, base_log, levels, batch, wp, wb,
-                                                   where, stream))
-
-    def sample_extract_batch(self, lwe_out, glwe, glwe_dim, index=0):
-        """lwe_out[b] = the LWE ciphertext (glwe_dim*n mask words, body last) of coefficient `index` of glwe[b] (glwe_dim+1 polynomials)."""
-        gp, gc, where, stream = self._words(glwe)
-        op, oc, ow, _ = self._words(lwe_out)
-        n = self._n
-        if glwe_dim < 0 or index < 0 or gc % ((glwe_dim + 1) * n) or ow != where or oc != gc // ((glwe_dim + 1) * n) * (glwe_dim * n + 1):
-            raise Panic("glwe: batch*(glwe_dim+1) polynomials; lwe_out: batch*(glwe_dim*n+1) words in the same memory")
-        check(lib().cntt_native_sample_extract_batch(self._h, op, gp, glwe_dim, index, gc // ((glwe_dim + 1) * n), where, stream))
+        """acc[b] = X^rot_t[lwe_dim][b] * lut, then for i < lwe_dim: acc[b] += ExtProd(bsk_i, X^rot_t[i][b] acc[b] - acc[b]) mod 2^w, in
+        place: the words of gadget_decompose_batch(mode="cmux") + external_product_batch(accumulate=True) per iteration.  acc:
+        batch*(glwe_dim+1) polynomials (written only); lut: glwe_dim+1 polynomials, or batch*(glwe_dim+1) (lut_per_element; None: told
+        by the size); rot_t: (lwe_dim+1)*batch uint32 as lwe_modswitch_batch writes them; workspace: None (one allocation per call) or a
+        buffer of pbs_workspace_bytes().  bsk_residues: NPRIMES buffers of lwe_dim*(glwe_dim+1)*levels*(glwe_dim+1) residue polynomials
+        as fwd_batch writes them for the key polynomials."""
+        self._blind_rotate(acc, lut, rot_t, bsk_residues, lwe_dim, glwe_dim, base_log, levels, workspace, lut_per_element)
 
     def bootstrap_batch(self, lwe_out, lwe_in, lut, bsk_residues, lwe_dim, glwe_dim, base_log, levels, workspace=None,
                         lut_per_element=None):
-        """lwe_modswitch_batch -> blind_rotate_batch -> sample_extract_batch(index=0) in one call: lwe_in batch*(lwe_dim+1) words,
-        lwe_out batch*(glwe_dim*n+1) words; rot_t and the accumulator live in the workspace (None: one allocation per call)."""
-        ip, ic, where, stream = self._words(lwe_in)
-        op, oc, ow, _ = self._words(lwe_out)
-        n = self._n
-        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or ic % (lwe_dim + 1) or ow != where:
-            raise Panic("lwe_in: batch*(lwe_dim+1) words; lwe_out in the same memory; base_log, levels >= 1")
-        batch = ic // (lwe_dim + 1)
-        if oc != batch * (glwe_dim * n + 1):
-            raise Panic("lwe_out must hold batch*(glwe_dim*n+1) = %d words" % (batch * (glwe_dim * n + 1)))
-        lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
-        keys = self._bsk(bsk_residues, where, lwe_dim, glwe_dim, levels)
-        wp, wb = self._workspace(workspace, where)
-        check(lib().cntt_native_bootstrap_batch(self._h, op, ip, lp, per, keys, lwe_dim, glwe_dim, base_log, levels, batch, wp, wb,
-                                                where, stream))
+        """lwe_modswitch_batch -> blind_rotate_batch -> sample_extract_batch(index=0) mod 2^w in one call: lwe_in batch*(lwe_dim+1)
+        words, lwe_out batch*(glwe_dim*n+1) words; rot_t and the accumulator live in the workspace (None: one allocation per call)."""
+        self._bootstrap(lwe_out, lwe_in, lut, bsk_residues, lwe_dim, glwe_dim, base_log, levels, workspace, lut_per_element)
 
     # -- LWE keyswitch, and keyswitch + bootstrap in one call (include/cntt_keyswitch.h) ------------------------------------------------
     def ks_pbs_workspace_bytes(self, lwe_dim, glwe_dim, levels, batch):

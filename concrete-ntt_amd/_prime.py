@@ -5,9 +5,10 @@ import numpy as np
 
 from . import _lib
 from ._lib import Panic, buffer_info, check, lib
+from ._pbs import PbsMixin
 
 
-class PrimePlan:
+class PrimePlan(PbsMixin):
     """Negacyclic NTT plan for a prime modulus; mirrors concrete_ntt::prime{32,64}::Plan
     (src/prime64.rs:221-236, :701-1129 ; src/prime32.rs:601-616, :627-927).
 
@@ -173,55 +174,12 @@ class PrimePlan:
             raise Panic("acc, lhs and rhs must have the same shape and live in the same memory")
         check(getattr(lib(), self._p + "mul_accumulate_batch")(self._h, ap, lp, rp, batch, where, stream))
 
-    # -- programmable bootstrap mod p (include/cntt_prime_pbs.h): decomposition, modulus switch, blind rotation, extraction ----------
-    SRC_MODES = {"plain": 0, "rotate": 1, "cmux": 2}
+    # -- programmable bootstrap mod p (include/cntt_prime_pbs.h): decomposition, modulus switch, blind rotation, extraction; the calls
+    #    themselves: PbsMixin ------------------------------------------------------------------------------------------------------------
+    _words = _arg
 
-    def _rot(self, rot, where, what):
-        rp, rc_, esz, rw, _ = buffer_info(rot)
-        if esz != 4 or rw != where:
-            raise Panic("%s: uint32 exponents in the memory of the other buffers" % what)
-        return rp, rc_
-
-    def gadget_decompose_batch(self, terms, polys, base_log, levels, rot=None, mode="plain"):
-        """terms[b][q*levels + l-1] = signed digit l (of `levels`, base_log bits each, d_1 most significant and unmasked) of the balanced
-        lift of the source polynomial of polys[b][q], stored canonically mod p: polys itself ("plain"), X^rot[b] * polys ("rotate") or
-        X^rot[b] * polys - polys ("cmux") in Z_p[X]/(X^n+1).  polys: batch*npolys polynomials; terms: batch*npolys*levels; npolys is
-        taken from len(rot) = batch when rot is given, else 1."""
-        if mode not in self.SRC_MODES:
-            raise Panic("mode must be one of %s" % sorted(self.SRC_MODES))
-        pp, pc, where, stream = self._arg(polys)
-        tp, tc, tw, _ = self._arg(terms)
-        rp = None
-        if rot is not None:
-            rp = self._rot(rot, where, "rot")
-        elif mode != "plain":
-            raise Panic("mode %r needs rot" % mode)
-        n = self._n
-        if levels <= 0 or base_log <= 0 or pc % n or tw != where or tc != pc * levels:
-            raise Panic("polys: batch*npolys polynomials; terms: levels times as many in the same memory; base_log, levels >= 1")
-        batch = rp[1] if rp else pc // n
-        if batch == 0 or (pc // n) % batch:
-            if pc:
-                raise Panic("polys must hold a whole number of polynomials per exponent in rot")
-            batch = 0
-        npolys = (pc // n) // batch if batch else 0
-        check(getattr(lib(), self._p + "gadget_decompose_batch")(self._h, tp, pp, rp[0] if rp else None, npolys, base_log, levels,
-                                                                 self.SRC_MODES[mode], batch, where, stream))
-
-    def pbs_workspace_bytes(self, lwe_dim, glwe_dim, levels, batch):
-        """Bytes of workspace bootstrap_batch needs (digits + rot_t + accumulator, each 256-byte aligned); enough for
-        blind_rotate_batch too."""
-        if min(lwe_dim, glwe_dim, levels, batch) < 0:
-            raise Panic("lwe_dim, glwe_dim, levels and batch must not be negative")
-        return getattr(lib(), self._p + "pbs_workspace_bytes")(self._h, lwe_dim, glwe_dim, levels, batch)
-
-    def _workspace(self, workspace, where):
-        if workspace is None:
-            return None, 0
-        ptr, count, esz, w, _ = buffer_info(workspace)
-        if w != where:
-            raise Panic("workspace must live in the memory of the other buffers")
-        return ptr, count * esz
+    def _fn(self, name):
+        return getattr(lib(), self._p + name)
 
     def _bsk(self, bsk_ntt, where, lwe_dim, glwe_dim, levels):
         kp, kc, kw, _ = self._arg(bsk_ntt)
@@ -229,73 +187,16 @@ class PrimePlan:
             raise Panic("bsk_ntt: lwe_dim*(glwe_dim+1)*levels*(glwe_dim+1) NTT-domain polynomials in the memory of the other buffers")
         return kp
 
-    def _lut(self, lut, lut_per_element, where, glwe_dim, batch):
-        lp, lc, lw, _ = self._arg(lut)
-        shared, each = (glwe_dim + 1) * self._n, batch * (glwe_dim + 1) * self._n
-        if lut_per_element is None:
-            lut_per_element = lc == each and lc != shared
-        if lw != where or lc != (each if lut_per_element else shared):
-            raise Panic("lut: glwe_dim+1 polynomials shared by the batch, or batch*(glwe_dim+1) with lut_per_element, in the memory "
-                        "of the other buffers")
-        return lp, 1 if lut_per_element else 0
-
-    def lwe_modswitch_batch(self, rot_t, lwe, lwe_dim):
-        """rot_t[i*batch + b] = round(lwe[b][i] * 2n / p) mod 2n (exact; p is odd, no ties) for the lwe_dim mask words, and 2n minus that
-        for the body in row lwe_dim.  lwe: batch*(lwe_dim+1) words; rot_t: (lwe_dim+1)*batch uint32, transposed: row i is iteration i's
-        rot."""
-        lp, lc, where, stream = self._arg(lwe)
-        if lwe_dim < 0 or lc % (lwe_dim + 1):
-            raise Panic("lwe: batch*(lwe_dim+1) words; rot_t: as many uint32 in the same memory")
-        rp, rc_ = self._rot(rot_t, where, "rot_t")
-        if rc_ != lc:
-            raise Panic("lwe: batch*(lwe_dim+1) words; rot_t: as many uint32 in the same memory")
-        check(getattr(lib(), self._p + "lwe_modswitch_batch")(self._h, rp, lp, lwe_dim, lc // (lwe_dim + 1), where, stream))
-
     def blind_rotate_batch(self, acc, lut, rot_t, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, workspace=None, lut_per_element=None):
         """acc[b] = X^rot_t[lwe_dim][b] * lut, then for i < lwe_dim: acc[b] += ExtProd(bsk_i, X^rot_t[i][b] acc[b] - acc[b]) mod p, in
         place: the words of gadget_decompose_batch(mode="cmux") + external_product_batch(accumulate=True) per iteration.  acc:
         batch*(glwe_dim+1) polynomials (written only); lut: glwe_dim+1 polynomials, or batch*(glwe_dim+1) (lut_per_element; None: told
-        by the size); rot_t: (lwe_dim+1)*batch uint32 as lwe_modswitch_batch writes them; bsk_ntt: ONE buffer of
-        lwe_dim*(glwe_dim+1)*levels*(glwe_dim+1) polynomials holding n^-1 * fwd(key) (fwd_batch, then normalize_batch); workspace: None
-        (one allocation per call) or a buffer of pbs_workspace_bytes()."""
-        ap, ac, where, stream = self._arg(acc)
-        n = self._n
-        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or ac % ((glwe_dim + 1) * n):
-            raise Panic("acc: batch*(glwe_dim+1) polynomials; base_log, levels >= 1")
-        batch = ac // ((glwe_dim + 1) * n)
-        rp, rc_ = self._rot(rot_t, where, "rot_t")
-        if rc_ != (lwe_dim + 1) * batch:
-            raise Panic("rot_t: (lwe_dim+1)*batch uint32 in the memory of acc")
-        lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
-        kp = self._bsk(bsk_ntt, where, lwe_dim, glwe_dim, levels)
-        wp, wb = self._workspace(workspace, where)
-        check(getattr(lib(), self._p + "blind_rotate_batch")(self._h, ap, lp, per, rp, kp, lwe_dim, glwe_dim, base_log, levels, batch, wp,
-                                                             wb, where, stream))
-
-    def sample_extract_batch(self, lwe_out, glwe, glwe_dim, index=0):
-        """lwe_out[b] = the LWE ciphertext (glwe_dim*n mask words, body last) of coefficient `index` of glwe[b] (glwe_dim+1 polynomials),
-        negations mod p."""
-        gp, gc, where, stream = self._arg(glwe)
-        op, oc, ow, _ = self._arg(lwe_out)
-        n = self._n
-        if glwe_dim < 0 or index < 0 or gc % ((glwe_dim + 1) * n) or ow != where or oc != gc // ((glwe_dim + 1) * n) * (glwe_dim * n + 1):
-            raise Panic("glwe: batch*(glwe_dim+1) polynomials; lwe_out: batch*(glwe_dim*n+1) words in the same memory")
-        check(getattr(lib(), self._p + "sample_extract_batch")(self._h, op, gp, glwe_dim, index, gc // ((glwe_dim + 1) * n), where,
-                                                               stream))
+        by the size); rot_t: (lwe_dim+1)*batch uint32 as lwe_modswitch_batch writes them; workspace: None (one allocation per call) or a
+        buffer of pbs_workspace_bytes().  bsk_ntt: ONE buffer of lwe_dim*(glwe_dim+1)*levels*(glwe_dim+1) polynomials holding n^-1 *
+        fwd(key) (fwd_batch, then normalize_batch)."""
+        self._blind_rotate(acc, lut, rot_t, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, workspace, lut_per_element)
 
     def bootstrap_batch(self, lwe_out, lwe_in, lut, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, workspace=None, lut_per_element=None):
-        """lwe_modswitch_batch -> blind_rotate_batch -> sample_extract_batch(index=0) in one call: lwe_in batch*(lwe_dim+1) words,
+        """lwe_modswitch_batch -> blind_rotate_batch -> sample_extract_batch(index=0) mod p in one call: lwe_in batch*(lwe_dim+1) words,
         lwe_out batch*(glwe_dim*n+1) words; rot_t and the accumulator live in the workspace (None: one allocation per call)."""
-        ip, ic, where, stream = self._arg(lwe_in)
-        op, oc, ow, _ = self._arg(lwe_out)
-        n = self._n
-        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or ic % (lwe_dim + 1) or ow != where:
-            raise Panic("lwe_in: batch*(lwe_dim+1) words; lwe_out in the same memory; base_log, levels >= 1")
-        batch = ic // (lwe_dim + 1)
-        if oc != batch * (glwe_dim * n + 1):
-            raise Panic("lwe_out must hold batch*(glwe_dim*n+1) = %d words" % (batch * (glwe_dim * n + 1)))
-        lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
-        kp = self._bsk(bsk_ntt, where, lwe_dim, glwe_dim, levels)
-        wp, wb = self._workspace(workspace, where)
-        check(getattr(lib(), self._p + "bootstrap_batch")(self._h, op, ip, lp, per, kp, lwe_dim, glwe_dim, base_log, levels, batch, wp, wb,
-                                                          where, stream))
+        self._bootstrap(lwe_out, lwe_in, lut, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, workspace, lut_per_element)

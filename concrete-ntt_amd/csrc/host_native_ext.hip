@@ -9,6 +9,7 @@
 #include "native_keyswitch.hpp"
 #include "native_pack.hpp"
 #include "native_pbs.hpp"
+#include "pbs_host.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // external product of the native plans (include/cntt_ext.h; no counterpart in the reference)
@@ -142,20 +143,6 @@ extern "C" int cntt_native_external_product_batch(const cntt_native_t *pl, void 
 // rotation / CMux difference / signed gadget decomposition and the external product on undecomposed polynomials
 // (include/cntt_gadget.h, native_gadget.hpp)
 // ---------------------------------------------------------------------------------------------
-static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return abytes && bbytes && x < y + bbytes && y < x + abytes;
-}
-// the checks the two calls share; wbits = word width of the kind
-static int gadget_check(const cntt_native *pl, unsigned base_log, unsigned levels, int mode, const uint32_t *rot) {
-    const unsigned wbits = 8u * (unsigned)pl->info.word;
-    if (base_log == 0) return fail(CNTT_EINVAL, "base_log is 0");
-    if (levels == 0) return fail(CNTT_EINVAL, "levels is 0");
-    if ((uint64_t)base_log * levels > wbits) return fail(CNTT_EINVAL, "base_log * levels = %u * %u exceeds the word width %u", base_log, levels, wbits);
-    if (mode != CNTT_SRC_PLAIN && mode != CNTT_SRC_ROTATE && mode != CNTT_SRC_CMUX) return fail(CNTT_EINVAL, "src_mode %d is not a cntt_src_mode_t", mode);
-    if (mode != CNTT_SRC_PLAIN && !rot) return fail(CNTT_EINVAL, "rot is NULL and src_mode reads it");
-    return CNTT_OK;
-}
 // off = 2^(s-1) + K 2^s mod 2^w, K = sum_l (B/2) B^(levels-l), s = w - base_log levels (native_gadget.hpp)
 static u128 gadget_offset(unsigned wbits, unsigned base_log, unsigned levels) {
     const unsigned s = wbits - base_log * levels;
@@ -202,34 +189,65 @@ static int native_gadget_device(const cntt_native *pl, void *terms, const void *
         return gadget_launch_w<decltype(w)>(terms, polys, rot, npolys, base_log, levels, mode, batch, native_logn(pl), st);
     });
 }
-// host path: the rotation exponents are in reach, so one that is not below 2n is an error there (`name`: the argument in the message)
-static int check_rot_host(const cntt_native *pl, const uint32_t *rot, size_t count, const char *name) {
-    for (size_t i = 0; i < count; ++i)
-        if ((size_t)rot[i] >= 2 * pl->n) return fail(CNTT_EINVAL, "%s[%zu] = %u is not below 2n = %zu", name, i, rot[i], 2 * pl->n);
-    return CNTT_OK;
-}
+
+// What the shared bootstrap pipeline (pbs_host.hpp) needs to know of the native plans: words of 4, 8 or 16 bytes behind void pointers, digits
+// of the whole word, and a key of one residue plane per prime.
+struct NativePbs {
+    using Plan = cntt_native;
+    using Word = void;
+    static constexpr const char *NAME = "native";
+    static size_t word(const cntt_native *pl) { return (size_t)pl->info.word; }
+    static int logn(const cntt_native *pl) { return native_logn(pl); }
+    static unsigned digit_bits(const cntt_native *pl) { return 8u * (unsigned)pl->info.word; }
+    static constexpr const char *DIGIT_BUDGET_MSG = "base_log * levels = %u * %u exceeds the word width %u";
+    static int check_terms(const cntt_native *pl, size_t glwe_dim, unsigned levels) {
+        const size_t nterms = (glwe_dim + 1) * levels;
+        if (nterms > pl->max_terms)
+            return fail(CNTT_EINVAL, "(glwe_dim + 1) * levels = %zu exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range",
+                        nterms, pl->max_terms);
+        return CNTT_OK;
+    }
+
+    using Key = const void *const *;
+    struct KeyStore {
+        const void *plane[10];
+    };
+    static int key_check(const cntt_native *pl, Key bsk) {
+        if (!bsk) return fail(CNTT_EINVAL, "bsk_ntt is NULL");
+        return check_key_planes(pl, bsk, "bsk_ntt");
+    }
+    static size_t key_bytes(const cntt_native *pl, size_t polys) { return polys * pl->n * pl->rbytes(); }
+    static Key key_in(const cntt_native *pl, Staging &s, Key bsk, size_t bytes, KeyStore &ks) {
+        key_planes_to_device(pl, s, bsk, bytes, ks.plane);
+        return ks.plane;
+    }
+    static Key key_at(const cntt_native *pl, Key bsk, size_t offset, KeyStore &ks) {
+        for (int j = 0; j < pl->info.nprimes; ++j) ks.plane[j] = static_cast<const char *>(bsk[j]) + offset;
+        return ks.plane;
+    }
+
+    static constexpr int MODSWITCH_MAX_LOGN = 30;   // ms() reads the top 32 bits
+    static constexpr int TILE = PBS_TILE;
+    static hipError_t launch_modswitch(const cntt_native *pl, uint32_t *rot_t, const void *lwe, size_t lwe_dim, size_t batch, unsigned grid,
+                                       hipStream_t st) {
+        return launch_native_lwe_modswitch(pl->info.word, rot_t, lwe, native_logn(pl), lwe_dim, batch, grid, st);
+    }
+    static hipError_t launch_pbs_init(const cntt_native *pl, void *acc, const void *lut, const uint32_t *rot, uint32_t npolys, bool per_element,
+                                      size_t batch, bool stream, unsigned grid, hipStream_t st) {
+        return launch_native_pbs_init(pl->info.word, acc, lut, rot, native_logn(pl), npolys, per_element, batch, stream, grid, st);
+    }
+    static hipError_t launch_sample_extract(const cntt_native *pl, void *lwe_out, const void *glwe, size_t glwe_dim, uint32_t index, size_t batch,
+                                            unsigned grid, hipStream_t st) {
+        return launch_native_sample_extract(pl->info.word, lwe_out, glwe, native_logn(pl), glwe_dim, index, batch, grid, st);
+    }
+    static constexpr auto gadget = native_gadget_device;   // the two steps of the loop
+    static constexpr auto ext_product = native_ext_device;
+};
 
 extern "C" int cntt_native_gadget_decompose_batch(const cntt_native_t *pl, void *terms, const void *polys, const uint32_t *rot,
                                                   size_t npolys, unsigned base_log, unsigned levels, cntt_src_mode_t src_mode, size_t batch,
                                                   cntt_mem_t where, void *stream) {
-    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
-    if (int rc = gadget_check(pl, base_log, levels, (int)src_mode, rot)) return rc;
-    if (batch == 0 || npolys == 0) return CNTT_OK;
-    if (!terms || !polys) return fail(CNTT_EINVAL, "NULL argument");
-    const size_t pb = batch * npolys * pl->n * (size_t)pl->info.word, tb = pb * levels;
-    if (ranges_overlap(terms, tb, polys, pb)) return fail(CNTT_EINVAL, "terms overlaps polys");
-    hipStream_t st = (hipStream_t)stream;
-    if (where == CNTT_MEM_DEVICE) return native_gadget_device(pl, terms, polys, rot, npolys, base_log, levels, (int)src_mode, batch, st);
-    const bool rotated = src_mode != CNTT_SRC_PLAIN;
-    if (rotated)
-        if (int rc = check_rot_host(pl, rot, batch, "rot")) return rc;
-    Staging s(st);
-    void *dt = s.out(terms, tb);
-    const void *dp = s.in(polys, pb);
-    const uint32_t *dr = rotated ? (const uint32_t *)s.in(rot, batch * sizeof(uint32_t)) : nullptr;
-    if (int rc = s.status()) return rc;
-    if (int rc = native_gadget_device(pl, dt, dp, dr, npolys, base_log, levels, (int)src_mode, batch, st)) return rc;
-    return s.finish();
+    return gadget_decompose<NativePbs>(pl, terms, polys, rot, npolys, base_log, levels, (int)src_mode, batch, where, (hipStream_t)stream);
 }
 
 // fused kernel (native_gadget.hpp): the 32- and 64-bit Plan32 kinds at 32 <= n <= 4096, base_log <= 31; FUSED_NONE elsewhere
@@ -288,7 +306,7 @@ extern "C" int cntt_native_external_product_decomposed_batch(const cntt_native_t
                                                              unsigned base_log, unsigned levels, cntt_src_mode_t src_mode, size_t nout,
                                                              size_t batch, cntt_mem_t where, void *stream) {
     if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
-    if (int rc = gadget_check(pl, base_log, levels, (int)src_mode, rot)) return rc;
+    if (int rc = gadget_check<NativePbs>(pl, base_log, levels, (int)src_mode, rot)) return rc;
     const size_t nterms = npolys * levels;
     if (nterms > pl->max_terms)
         return fail(CNTT_EINVAL, "npolys * levels = %zu exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range", nterms,
@@ -307,7 +325,7 @@ extern "C" int cntt_native_external_product_decomposed_batch(const cntt_native_t
         return native_ext_gadget_device(pl, out, polys, rot, addend, key_ntt, npolys, base_log, levels, (int)src_mode, nout, batch, st);
     const bool rotated = nterms && src_mode != CNTT_SRC_PLAIN;
     if (rotated)
-        if (int rc = check_rot_host(pl, rot, batch, "rot")) return rc;
+        if (int rc = check_rot_host(pl->n, rot, batch, "rot")) return rc;
     Staging s(st);
     const void *dkey[10];
     key_planes_to_device(pl, s, key_ntt, nterms * nout * n * pl->rbytes(), dkey);
@@ -323,202 +341,28 @@ extern "C" int cntt_native_external_product_decomposed_batch(const cntt_native_t
 // ---------------------------------------------------------------------------------------------
 // programmable bootstrap: modulus switch, blind rotation in place, sample extraction (include/cntt_pbs.h, native_pbs.hpp)
 // ---------------------------------------------------------------------------------------------
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-// the three parts of the workspace, in bytes and in this order (cntt_pbs.h states the formula)
-struct PbsSizes {
-    size_t digits, rot, acc;
-    size_t total() const { return up256(digits) + up256(rot) + up256(acc); }
-};
-static PbsSizes pbs_sizes(const cntt_native *pl, size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) {
-    const size_t pb = batch * (glwe_dim + 1) * pl->n * (size_t)pl->info.word;
-    return PbsSizes{pb * levels, (lwe_dim + 1) * batch * sizeof(uint32_t), pb};
-}
 extern "C" size_t cntt_native_pbs_workspace_bytes(const cntt_native_t *pl, size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) {
-    return pl ? pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch).total() : 0;
+    return pbs_workspace_bytes<NativePbs>(pl, lwe_dim, glwe_dim, levels, batch);
 }
-
-static int native_modswitch_device(const cntt_native *pl, uint32_t *rot_t, const void *lwe, size_t lwe_dim, size_t batch, hipStream_t st) {
-    if (native_logn(pl) > 30) return fail(CNTT_EINVAL, "ntt_size too large for the modulus switch");   // ms() reads the top 32 bits
-    const size_t tiles = ((lwe_dim + PBS_TILE) / PBS_TILE) * ((batch + PBS_TILE - 1) / PBS_TILE);
-    const hipError_t e = launch_native_lwe_modswitch(pl->info.word, rot_t, lwe, native_logn(pl), lwe_dim, batch, ew_grid(tiles * 256), st);
-    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_lwe_modswitch_kernel launch failed: %s", hipGetErrorString(e));
-    return CNTT_OK;
-}
-static int native_extract_device(const cntt_native *pl, void *lwe_out, const void *glwe, size_t glwe_dim, size_t index, size_t batch,
-                                 hipStream_t st) {
-    const hipError_t e = launch_native_sample_extract(pl->info.word, lwe_out, glwe, native_logn(pl), glwe_dim, (uint32_t)index, batch,
-                                                      ew_grid(batch * (glwe_dim * pl->n + 1)), st);
-    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_sample_extract_kernel launch failed: %s", hipGetErrorString(e));
-    return CNTT_OK;
-}
-// acc = X^(body row of rot_t) lut, then lwe_dim times decomposition (CMux difference) into `digits` and the external product accumulating
-// into acc.  In place is sound: the digits are complete before the product starts (stream order), the product reads only the digits and
-// the key, and each of its launches of two outputs reads and writes only its own outputs.
-static int native_blind_rotate_device(const cntt_native *pl, void *acc, const void *lut, bool lut_per_element, const uint32_t *rot_t,
-                                      const void *const *bsk, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels,
-                                      size_t batch, void *digits, hipStream_t st) {
-    const size_t npolys = glwe_dim + 1, nterms = npolys * levels, n = pl->n, w = (size_t)pl->info.word;
-    const size_t slice = nterms * npolys * n * pl->rbytes();   // one iteration's key, bytes per plane
-    const hipError_t e = launch_native_pbs_init(pl->info.word, acc, lut, rot_t + lwe_dim * batch, native_logn(pl), (uint32_t)npolys,
-                                                lut_per_element, batch, batch * npolys * n * w > STREAM_BYTES,
-                                                ew_grid(batch * npolys * n * w / 16), st);
-    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_pbs_init_kernel launch failed: %s", hipGetErrorString(e));
-    const int k = pl->info.nprimes;
-    const void *key[10];
-    for (size_t i = 0; i < lwe_dim; ++i) {
-        for (int j = 0; j < k; ++j) key[j] = static_cast<const char *>(bsk[j]) + i * slice;
-        if (int rc = native_gadget_device(pl, digits, acc, rot_t + i * batch, npolys, base_log, levels, CNTT_SRC_CMUX, batch, st)) return rc;
-        if (int rc = native_ext_device(pl, acc, digits, key, nterms, npolys, batch, true, st)) return rc;
-    }
-    return CNTT_OK;
-}
-
 extern "C" int cntt_native_lwe_modswitch_batch(const cntt_native_t *pl, uint32_t *rot_t, const void *lwe, size_t lwe_dim, size_t batch,
                                                cntt_mem_t where, void *stream) {
-    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
-    if (batch == 0) return CNTT_OK;
-    if (!rot_t) return fail(CNTT_EINVAL, "rot_t is NULL");
-    if (!lwe) return fail(CNTT_EINVAL, "lwe is NULL");
-    const size_t rb = (lwe_dim + 1) * batch * sizeof(uint32_t), lb = (lwe_dim + 1) * batch * (size_t)pl->info.word;
-    if (ranges_overlap(rot_t, rb, lwe, lb)) return fail(CNTT_EINVAL, "rot_t overlaps lwe");
-    hipStream_t st = (hipStream_t)stream;
-    if (where == CNTT_MEM_DEVICE) return native_modswitch_device(pl, rot_t, lwe, lwe_dim, batch, st);
-    Staging s(st);
-    uint32_t *dr = (uint32_t *)s.out(rot_t, rb);
-    const void *dl = s.in(lwe, lb);
-    if (int rc = s.status()) return rc;
-    if (int rc = native_modswitch_device(pl, dr, dl, lwe_dim, batch, st)) return rc;
-    return s.finish();
+    return lwe_modswitch<NativePbs>(pl, rot_t, lwe, lwe_dim, batch, where, (hipStream_t)stream);
 }
-
 extern "C" int cntt_native_sample_extract_batch(const cntt_native_t *pl, void *lwe_out, const void *glwe, size_t glwe_dim, size_t index,
                                                 size_t batch, cntt_mem_t where, void *stream) {
-    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
-    if (index >= pl->n) return fail(CNTT_EINVAL, "index = %zu is not below ntt_size = %zu", index, pl->n);
-    if (batch == 0) return CNTT_OK;
-    if (!lwe_out) return fail(CNTT_EINVAL, "lwe_out is NULL");
-    if (!glwe) return fail(CNTT_EINVAL, "glwe is NULL");
-    const size_t w = (size_t)pl->info.word, ob = batch * (glwe_dim * pl->n + 1) * w, gb = batch * (glwe_dim + 1) * pl->n * w;
-    if (ranges_overlap(lwe_out, ob, glwe, gb)) return fail(CNTT_EINVAL, "lwe_out overlaps glwe");
-    hipStream_t st = (hipStream_t)stream;
-    if (where == CNTT_MEM_DEVICE) return native_extract_device(pl, lwe_out, glwe, glwe_dim, index, batch, st);
-    Staging s(st);
-    void *dout = s.out(lwe_out, ob);
-    const void *dg = s.in(glwe, gb);
-    if (int rc = s.status()) return rc;
-    if (int rc = native_extract_device(pl, dout, dg, glwe_dim, index, batch, st)) return rc;
-    return s.finish();
-}
-
-// the argument checks blind_rotate and bootstrap share, up to the NULL key planes; `need` = what the workspace must hold
-static int pbs_check(const cntt_native *pl, const void *const *bsk, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels,
-                     size_t batch, const void *workspace, size_t workspace_bytes, size_t need) {
-    const uint32_t some_rot = 0;
-    if (int rc = gadget_check(pl, base_log, levels, CNTT_SRC_CMUX, &some_rot)) return rc;
-    if (glwe_dim + 1 >= ((size_t)1 << 32)) return fail(CNTT_EINVAL, "glwe_dim too large");
-    const size_t nterms = (glwe_dim + 1) * levels;
-    if (nterms > pl->max_terms)
-        return fail(CNTT_EINVAL, "(glwe_dim + 1) * levels = %zu exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range",
-                    nterms, pl->max_terms);
-    if (batch == 0) return CNTT_OK;
-    if (lwe_dim) {
-        if (!bsk) return fail(CNTT_EINVAL, "bsk_ntt is NULL");
-        if (int rc = check_key_planes(pl, bsk, "bsk_ntt")) return rc;
-    }
-    if (workspace) {
-        if ((uintptr_t)workspace % 16) return fail(CNTT_EINVAL, "workspace is not 16-byte aligned");
-        if (workspace_bytes < need) return fail(CNTT_EINVAL, "workspace_bytes = %zu is below the %zu bytes this call needs", workspace_bytes, need);
-    }
-    return CNTT_OK;
+    return sample_extract<NativePbs>(pl, lwe_out, glwe, glwe_dim, index, batch, where, (hipStream_t)stream);
 }
 extern "C" int cntt_native_blind_rotate_batch(const cntt_native_t *pl, void *acc, const void *lut, int lut_per_element, const uint32_t *rot_t,
                                               const void *const *bsk_ntt, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels,
                                               size_t batch, void *workspace, size_t workspace_bytes, cntt_mem_t where, void *stream) {
-    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
-    if (batch && !rot_t) return fail(CNTT_EINVAL, "rot_t is NULL");
-    const PbsSizes Z = pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch);
-    if (int rc = pbs_check(pl, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, Z.digits)) return rc;
-    if (batch == 0) return CNTT_OK;
-    if (!acc) return fail(CNTT_EINVAL, "acc is NULL");
-    if (!lut) return fail(CNTT_EINVAL, "lut is NULL");
-    const size_t lb = lut_per_element ? Z.acc : Z.acc / batch;
-    if (ranges_overlap(acc, Z.acc, lut, lb)) return fail(CNTT_EINVAL, "acc overlaps lut");
-    if (ranges_overlap(acc, Z.acc, rot_t, Z.rot)) return fail(CNTT_EINVAL, "acc overlaps rot_t");
-    if (workspace && ranges_overlap(acc, Z.acc, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "acc overlaps workspace");
-    hipStream_t st = (hipStream_t)stream;
-    if (where == CNTT_MEM_DEVICE) {
-        void *digits = workspace;
-        if (!digits && lwe_dim) HIP_TRY(hipMallocAsync(&digits, Z.digits, st));   // one allocation for the whole loop
-        const int rc = native_blind_rotate_device(pl, acc, lut, lut_per_element != 0, rot_t, bsk_ntt, lwe_dim, glwe_dim, base_log, levels,
-                                                  batch, digits, st);
-        if (!workspace && digits) (void)hipFreeAsync(digits, st);
-        return rc;
-    }
-    if (int rc = check_rot_host(pl, rot_t, (lwe_dim + 1) * batch, "rot_t")) return rc;
-    const size_t kb = lwe_dim * (glwe_dim + 1) * levels * (glwe_dim + 1) * pl->n * pl->rbytes();
-    Staging s(st);
-    const void *dkey[10];
-    if (lwe_dim) key_planes_to_device(pl, s, bsk_ntt, kb, dkey);
-    const void *dlut = s.in(lut, lb);
-    const uint32_t *drot = (const uint32_t *)s.in(rot_t, Z.rot);
-    void *dacc = s.out(acc, Z.acc), *ddig = s.alloc(Z.digits);
-    if (int rc = s.status()) return rc;
-    if (int rc = native_blind_rotate_device(pl, dacc, dlut, lut_per_element != 0, drot, dkey, lwe_dim, glwe_dim, base_log, levels, batch, ddig, st))
-        return rc;
-    return s.finish();
+    return blind_rotate<NativePbs>(pl, acc, lut, lut_per_element, rot_t, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace,
+                                   workspace_bytes, where, (hipStream_t)stream);
 }
-
-// modulus switch -> blind rotation -> extraction of coefficient 0 on device buffers; ws holds digits | rot_t | acc (PbsSizes)
-static int native_bootstrap_device(const cntt_native *pl, void *lwe_out, const void *lwe_in, const void *lut, bool lut_per_element,
-                                   const void *const *bsk, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels, size_t batch,
-                                   const PbsSizes &Z, char *ws, hipStream_t st) {
-    uint32_t *rot_t = reinterpret_cast<uint32_t *>(ws + up256(Z.digits));
-    void *acc = ws + up256(Z.digits) + up256(Z.rot);
-    if (int rc = native_modswitch_device(pl, rot_t, lwe_in, lwe_dim, batch, st)) return rc;
-    if (int rc = native_blind_rotate_device(pl, acc, lut, lut_per_element, rot_t, bsk, lwe_dim, glwe_dim, base_log, levels, batch, ws, st))
-        return rc;
-    return native_extract_device(pl, lwe_out, acc, glwe_dim, 0, batch, st);
-}
-
 extern "C" int cntt_native_bootstrap_batch(const cntt_native_t *pl, void *lwe_out, const void *lwe_in, const void *lut, int lut_per_element,
                                            const void *const *bsk_ntt, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels,
                                            size_t batch, void *workspace, size_t workspace_bytes, cntt_mem_t where, void *stream) {
-    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
-    const PbsSizes Z = pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch);
-    if (int rc = pbs_check(pl, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, Z.total())) return rc;
-    if (batch == 0) return CNTT_OK;
-    if (!lwe_out) return fail(CNTT_EINVAL, "lwe_out is NULL");
-    if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
-    if (!lut) return fail(CNTT_EINVAL, "lut is NULL");
-    const size_t w = (size_t)pl->info.word, ob = batch * (glwe_dim * pl->n + 1) * w, ib = batch * (lwe_dim + 1) * w;
-    const size_t lb = lut_per_element ? Z.acc : Z.acc / batch;
-    if (ranges_overlap(lwe_out, ob, lwe_in, ib)) return fail(CNTT_EINVAL, "lwe_out overlaps lwe_in");
-    if (ranges_overlap(lwe_out, ob, lut, lb)) return fail(CNTT_EINVAL, "lwe_out overlaps lut");
-    if (workspace) {
-        if (ranges_overlap(lwe_out, ob, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_out overlaps workspace");
-        if (ranges_overlap(lwe_in, ib, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_in overlaps workspace");
-        if (ranges_overlap(lut, lb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lut overlaps workspace");
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (where == CNTT_MEM_DEVICE) {
-        void *ws = workspace;
-        if (!ws) HIP_TRY(hipMallocAsync(&ws, Z.total(), st));   // one allocation for the whole call
-        const int rc = native_bootstrap_device(pl, lwe_out, lwe_in, lut, lut_per_element != 0, bsk_ntt, lwe_dim, glwe_dim, base_log, levels,
-                                               batch, Z, static_cast<char *>(ws), st);
-        if (!workspace) (void)hipFreeAsync(ws, st);
-        return rc;
-    }
-    const size_t kb = lwe_dim * (glwe_dim + 1) * levels * (glwe_dim + 1) * pl->n * pl->rbytes();
-    Staging s(st);
-    const void *dkey[10];
-    if (lwe_dim) key_planes_to_device(pl, s, bsk_ntt, kb, dkey);
-    const void *din = s.in(lwe_in, ib), *dlut = s.in(lut, lb);
-    void *dout = s.out(lwe_out, ob), *dws = s.alloc(Z.total());
-    if (int rc = s.status()) return rc;
-    if (int rc = native_bootstrap_device(pl, dout, din, dlut, lut_per_element != 0, dkey, lwe_dim, glwe_dim, base_log, levels, batch, Z,
-                                         static_cast<char *>(dws), st))
-        return rc;
-    return s.finish();
+    return bootstrap<NativePbs>(pl, lwe_out, lwe_in, lut, lut_per_element, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace,
+                                workspace_bytes, where, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -576,7 +420,7 @@ extern "C" int cntt_native_keyswitch_batch(const cntt_native_t *pl, void *lwe_ou
 // bytes of the keyswitched ciphertexts, which follow the bootstrap's part of the workspace (cntt_keyswitch.h states the formula)
 static size_t ks_mid_bytes(const cntt_native *pl, size_t lwe_dim, size_t batch) { return batch * (lwe_dim + 1) * (size_t)pl->info.word; }
 extern "C" size_t cntt_native_ks_pbs_workspace_bytes(const cntt_native_t *pl, size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) {
-    return pl ? pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch).total() + up256(ks_mid_bytes(pl, lwe_dim, batch)) : 0;
+    return pl ? pbs_sizes<NativePbs>(pl, lwe_dim, glwe_dim, levels, batch).total() + up256(ks_mid_bytes(pl, lwe_dim, batch)) : 0;
 }
 
 extern "C" int cntt_native_keyswitch_bootstrap_batch(const cntt_native_t *pl, void *lwe_out, const void *lwe_in, const void *ksk,
@@ -586,9 +430,9 @@ extern "C" int cntt_native_keyswitch_bootstrap_batch(const cntt_native_t *pl, vo
                                                      cntt_mem_t where, void *stream) {
     if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
     if (int rc = keyswitch_check(pl, lwe_dim, row_stride, ks_base_log, ks_levels, "ks_")) return rc;
-    const PbsSizes Z = pbs_sizes(pl, lwe_dim, glwe_dim, levels, batch);
+    const PbsSizes Z = pbs_sizes<NativePbs>(pl, lwe_dim, glwe_dim, levels, batch);
     const size_t mid = ks_mid_bytes(pl, lwe_dim, batch), need = Z.total() + up256(mid);
-    if (int rc = pbs_check(pl, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, need)) return rc;
+    if (int rc = pbs_check<NativePbs>(pl, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, need)) return rc;
     if (batch == 0) return CNTT_OK;
     if (!lwe_out) return fail(CNTT_EINVAL, "lwe_out is NULL");
     if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
@@ -611,7 +455,7 @@ extern "C" int cntt_native_keyswitch_bootstrap_batch(const cntt_native_t *pl, vo
     auto run = [&](void *out, const void *in, const void *key, const void *table, const void *const *bsk, char *ws) {
         void *lwe_mid = ws + Z.total();
         if (int rc = native_keyswitch_device(pl, lwe_mid, in, key, big, lwe_dim, row_stride, ks_base_log, ks_levels, batch, st)) return rc;
-        return native_bootstrap_device(pl, out, lwe_mid, table, lut_per_element != 0, bsk, lwe_dim, glwe_dim, base_log, levels, batch, Z, ws, st);
+        return bootstrap_device<NativePbs>(pl, out, lwe_mid, table, lut_per_element != 0, bsk, lwe_dim, glwe_dim, base_log, levels, batch, Z, ws, st);
     };
     if (where == CNTT_MEM_DEVICE) {
         void *ws = workspace;
@@ -647,7 +491,7 @@ extern "C" size_t cntt_native_pack_workspace_bytes(const cntt_native_t *pl, size
 }
 
 // out = the body polynomial, then per chunk of mask words the negated digit polynomials into `terms` and the external product
-// accumulating into out.  In place is sound as in native_blind_rotate_device: a chunk's terms are complete before its product starts
+// accumulating into out.  In place is sound as in blind_rotate_device (pbs_host.hpp): a chunk's terms are complete before its product starts
 // and rewritten only after it (stream order), and the product reads only the terms and the key.
 static int native_pack_device(const cntt_native *pl, void *out, const void *in, const void *const *pksk, size_t lin, size_t m, size_t glwe_dim,
                               unsigned base_log, unsigned levels, size_t batch, void *terms, hipStream_t st) {
@@ -674,7 +518,7 @@ extern "C" int cntt_native_pack_keyswitch_batch(const cntt_native_t *pl, void *g
                                                 size_t lwe_dim_in, size_t lwe_count, size_t glwe_dim, unsigned base_log, unsigned levels,
                                                 size_t batch, void *workspace, size_t workspace_bytes, cntt_mem_t where, void *stream) {
     if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
-    if (int rc = gadget_check(pl, base_log, levels, CNTT_SRC_PLAIN, nullptr)) return rc;
+    if (int rc = gadget_check<NativePbs>(pl, base_log, levels, CNTT_SRC_PLAIN, nullptr)) return rc;
     if (levels > pl->max_terms)
         return fail(CNTT_EINVAL, "levels = %u exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range", levels,
                     pl->max_terms);
@@ -692,8 +536,7 @@ extern "C" int cntt_native_pack_keyswitch_batch(const cntt_native_t *pl, void *g
     const size_t need = up256(pack_terms_bytes(pl, lwe_dim_in, levels, batch));
     if (ranges_overlap(glwe_out, ob, lwe_in, ib)) return fail(CNTT_EINVAL, "glwe_out overlaps lwe_in");
     if (workspace) {
-        if ((uintptr_t)workspace % 16) return fail(CNTT_EINVAL, "workspace is not 16-byte aligned");
-        if (workspace_bytes < need) return fail(CNTT_EINVAL, "workspace_bytes = %zu is below the %zu bytes this call needs", workspace_bytes, need);
+        if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
         if (ranges_overlap(glwe_out, ob, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "glwe_out overlaps workspace");
         if (ranges_overlap(lwe_in, ib, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_in overlaps workspace");
     }
