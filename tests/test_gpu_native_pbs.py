@@ -293,6 +293,41 @@ def test_blind_rotate_equals_per_iteration_calls_composed_n8192():
         check_blind_rotate(torch, "native64_plan32", 8192, k, per_element, with_ws)
 
 
+STREAM_BYTES = 384 << 20   # the library's streaming threshold (host_common.hpp)
+
+
+@pytest.mark.parametrize("w,per_element", [(32, True), (64, False), (128, False)])
+def test_blind_rotate_set_up_of_a_streaming_batch(w, per_element):
+    """native_pbs_init_kernel<W, true> on the three word widths: blind_rotate_batch with lwe_dim = 0 is the set-up alone (acc = X^rot
+    lut: no digits, no key); the first batch whose accumulator passes the streaming threshold (non-temporal stores) at n = 1024, k = 1,
+    against the same call made in two halves, which do not stream, on every word, and against the model on the first, the last and 32
+    sampled elements."""
+    torch = _torch()
+    n, k = 1024, 1
+    plan = WORDS[w].try_new(n)
+    pe = (k + 1) * per(plan)          # array elements per batch element
+    batch = STREAM_BYTES // ((k + 1) * n * plan.WORD) + 1
+    tt, lo, hi = (torch.int32, -2 ** 31, 2 ** 31 - 1) if w == 32 else (torch.int64, -2 ** 63, 2 ** 63 - 1)
+    g = torch.Generator(device="cuda").manual_seed(w)
+    lut = torch.randint(lo, hi, ((batch if per_element else 1) * pe,), dtype=tt, device="cuda", generator=g)
+    rot = torch.randint(0, 2 * n, (batch,), dtype=torch.int32, device="cuda", generator=g)
+    nokey = [torch.empty(0, dtype=torch.int32, device="cuda") for _ in range(plan.NPRIMES)]
+    acc = torch.empty(batch * pe, dtype=tt, device="cuda")
+    plan.blind_rotate_batch(acc, lut, rot, nokey, 0, k, 7, 3, lut_per_element=per_element)
+    half = batch // 2
+    small = torch.empty((batch - half) * pe, dtype=tt, device="cuda")
+    plan.blind_rotate_batch(small[:half * pe], lut[:half * pe] if per_element else lut, rot[:half], nokey, 0, k, 7, 3, lut_per_element=per_element)
+    assert torch.equal(small[:half * pe], acc[:half * pe])
+    plan.blind_rotate_batch(small, lut[half * pe:] if per_element else lut, rot[half:], nokey, 0, k, 7, 3, lut_per_element=per_element)
+    assert torch.equal(small, acc[half * pe:])
+    rot_h = rot.cpu().tolist()
+    rng = np.random.default_rng(seed("stream-init", w))
+    for b in sorted({0, batch - 1} | {int(x) for x in rng.integers(0, batch, size=32)}):
+        f = to_ints(plan, host(lut[b * pe:(b + 1) * pe] if per_element else lut, plan.word_dtype))
+        want = [x for q in range(k + 1) for x in source(f[q * n:(q + 1) * n], rot_h[b], w, "rotate")]
+        assert to_ints(plan, host(acc[b * pe:(b + 1) * pe], plan.word_dtype)) == want, (w, "element", b)
+
+
 # -- 4. blind rotation against the big-integer model and the oracle -----------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["native64_plan32", "native_binary32_plan32"])
 def test_blind_rotate_matches_model_and_oracle(oracle, kind):

@@ -4,9 +4,11 @@ per-iteration public calls it replaces (both buffers compared whole) and, at n <
 cntt_prime*_bootstrap_batch against its three steps; graph capture; the C example.  The one check with a tolerance is the functional
 test, whose bound is derived in its docstring.
 
-Strict-range primes (2^62 <= p < 2^63, here P63): the reference's Barrett wrap makes mul_accumulate differ
-from the exact product mod p, so P63 runs the comparisons against the public calls and the decomposition / modswitch / extract model
-checks only, never the big-integer product model."""
+Strict-range primes (2^62 <= p < 2^63, 2^30 <= p < 2^31): the reference's Barrett wrap can make mul_accumulate
+differ from the exact product mod p.  Whether it does is a property of the prime, not of the range -- P63 and P31 lie right below
+2^63 and 2^31, where the estimate never passes the word -- so the big-integer product model runs for the primes of EXACT, which a probe
+on the CPU oracle selects (random_cases.model_applies); a prime outside it (PW63, PW31: strict-range primes whose products do wrap) runs the comparisons
+against the public calls and the decomposition / modswitch / extract model checks only."""
 import os
 import subprocess
 import zlib
@@ -21,8 +23,17 @@ from test_prime_pbs_model import (P30, P32, P50, P62, P63, PM64, digits, edge_wo
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ALL = [P62, PM64, P50, P63, P30, P32]
-EXACT = [P62, PM64, P50, P30, P32]          # every prime outside the strict range: the big-integer model applies
+PG64 = 9224497936763846657          # 64-bit Montgomery class: p >= 2^63 and not 2^64 - c
+P51 = 2251799813554177              # below 2^51 (the second 64-bit class on doubles)
+P31 = 2147352577                    # 32-bit strict range
+PA62 = 2305843009214414849          # lazy, just above 2^61: the reference's Barrett estimate reaches 2p (the parity fix in inv)
+PA30 = 536903681                    # the same on 32-bit words, just above 2^29
+PW63 = 8717305756806021121          # strict range, where the reference's Barrett product does wrap: the probe rejects it
+PW31 = 2088517633                   # the same on 32-bit words (1 mod 2^14 only)
+ALL = [P62, PM64, P50, P63, P30, P32, PG64, P51, P31, PA62, PA30, PW63, PW31]
+# the primes for which the big-integer model applies: the oracle's fwd / mul_accumulate / inv composition equals the exact product on
+# the fixed probe of random_cases.model_applies (asserted in tests/test_random_cases.py, on the CPU)
+EXACT = [P62, PM64, P50, P63, P30, P32, PG64, P51, P31, PA62, PA30]
 
 
 def _torch():
@@ -51,6 +62,11 @@ def min_n(p):
 
 def dt(p):
     return np.uint64 if is64(p) else np.uint32
+
+
+def max_logn(p):
+    """the largest log2 n with p = 1 mod 2n"""
+    return ((p - 1) & -(p - 1)).bit_length() - 2
 
 
 def dev(torch, a):
@@ -176,6 +192,75 @@ def test_decomposition_on_the_host_path_and_noncanonical_words_do_not_fault():
     assert [int(x) for x in host(out, np.uint64)[4 * n:]] == want
 
 
+STREAM_BYTES = 384 << 20   # the library's streaming threshold (host_common.hpp)
+
+
+def sampled_elements(rng, batch, count=32):
+    return sorted({0, batch - 1} | {int(x) for x in rng.integers(0, batch, size=count)})
+
+
+def device_words(torch, p, count, g):
+    t = torch.randint(0, p, (count,), dtype=torch.int64, device="cuda", generator=g)
+    return t if is64(p) else t.to(torch.int32)
+
+
+@pytest.mark.parametrize("p", [P62, P30])
+def test_decomposition_of_a_streaming_batch(p):
+    """prime_gadget_kernel<T, true> on both word types: the first batch whose terms pass the streaming threshold (non-temporal stores)
+    at n = 1024, 2 polynomials per element, 4 levels, against the same call made in two halves, which do not stream, on every word, and
+    against the model on the first, the last and 32 sampled elements."""
+    torch = _torch()
+    n, npolys, beta, ell = 1024, 2, 7, 4
+    per = npolys * n
+    batch = STREAM_BYTES // (npolys * ell * n * dt(p)().itemsize) + 1
+    plan = make_plan(p, n)
+    g = torch.Generator(device="cuda").manual_seed(5)
+    polys = device_words(torch, p, batch * per, g)
+    rot = torch.randint(0, 2 * n, (batch,), dtype=torch.int32, device="cuda", generator=g)
+    terms = torch.empty(batch * per * ell, dtype=polys.dtype, device="cuda")
+    plan.gadget_decompose_batch(terms, polys, beta, ell, rot=rot, mode="cmux")
+    half = batch // 2
+    small = torch.empty((batch - half) * per * ell, dtype=polys.dtype, device="cuda")
+    plan.gadget_decompose_batch(small[:half * per * ell], polys[:half * per], beta, ell, rot=rot[:half], mode="cmux")
+    assert torch.equal(small[:half * per * ell], terms[:half * per * ell])
+    plan.gadget_decompose_batch(small, polys[half * per:], beta, ell, rot=rot[half:], mode="cmux")
+    assert torch.equal(small, terms[half * per * ell:])
+    rot_h = rot.cpu().tolist()
+    for b in sampled_elements(np.random.default_rng(seed("stream", p)), batch):
+        f = host(polys[b * per:(b + 1) * per], dt(p)).tolist()
+        want = [x for t in model_terms_element([f[q * n:(q + 1) * n] for q in range(npolys)], rot_h[b], p, beta, ell) for x in t]
+        assert host(terms[b * per * ell:(b + 1) * per * ell], dt(p)).tolist() == want, (p, "element", b)
+
+
+@pytest.mark.parametrize("p,per_element", [(P62, False), (P30, True)])
+def test_blind_rotate_set_up_of_a_streaming_batch(p, per_element):
+    """prime_pbs_init_kernel<T, true> on both word types: blind_rotate_batch with lwe_dim = 0 is the set-up alone (acc = X^rot lut: no
+    digits, no key); the first batch whose accumulator passes the streaming threshold at n = 1024, k = 1, against the same call in two
+    halves on every word and against the model on the first, the last and 32 sampled elements."""
+    torch = _torch()
+    n, k = 1024, 1
+    per = (k + 1) * n
+    batch = STREAM_BYTES // (per * dt(p)().itemsize) + 1
+    plan = make_plan(p, n)
+    g = torch.Generator(device="cuda").manual_seed(6)
+    lut = device_words(torch, p, (batch if per_element else 1) * per, g)
+    rot = torch.randint(0, 2 * n, (batch,), dtype=torch.int32, device="cuda", generator=g)
+    nokey = torch.empty(0, dtype=lut.dtype, device="cuda")
+    acc = torch.empty(batch * per, dtype=lut.dtype, device="cuda")
+    plan.blind_rotate_batch(acc, lut, rot, nokey, 0, k, 7, 3, lut_per_element=per_element)
+    half = batch // 2
+    small = torch.empty((batch - half) * per, dtype=lut.dtype, device="cuda")
+    plan.blind_rotate_batch(small[:half * per], lut[:half * per] if per_element else lut, rot[:half], nokey, 0, k, 7, 3, lut_per_element=per_element)
+    assert torch.equal(small[:half * per], acc[:half * per])
+    plan.blind_rotate_batch(small, lut[half * per:] if per_element else lut, rot[half:], nokey, 0, k, 7, 3, lut_per_element=per_element)
+    assert torch.equal(small, acc[half * per:])
+    rot_h = rot.cpu().tolist()
+    for b in sampled_elements(np.random.default_rng(seed("stream-init", p)), batch):
+        f = host(lut[b * per:(b + 1) * per] if per_element else lut, dt(p)).tolist()
+        want = [x for q in range(k + 1) for x in source(f[q * n:(q + 1) * n], rot_h[b], p, "rotate")]
+        assert host(acc[b * per:(b + 1) * per], dt(p)).tolist() == want, (p, "element", b)
+
+
 # -- 2. modulus switch -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("logn", range(4, 16))
 @pytest.mark.parametrize("p", ALL)
@@ -183,6 +268,7 @@ def test_modswitch_matches_model(p, logn):
     torch = _torch()
     if (1 << logn) < min_n(p):
         logn = 5          # the smallest prime32 plan (the case runs twice rather than being skipped)
+    logn = min(logn, max_logn(p))          # PA30 = 1 mod 2^15, PW31 = 1 mod 2^14 only: their largest plan, likewise
     plan = make_plan(p, 1 << logn)
     rng = np.random.default_rng(seed("ms", p, logn))
     special = modswitch_words(p, logn, rng)

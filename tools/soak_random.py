@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Extended run of the seeded random GPU parity sweeps (tests/test_gpu_random.py) over many more seeds than the
-test suite uses: prime plans, native polymul plans, product plans.  Prints the failing seeds, if any.
-    python tools/soak_random.py [extra_seeds_per_family] [plans|native|product|chain|wrap]
+test suite uses: prime plans, native polymul plans, product plans, multi-trip chains, the strict class's wrap zone, and the
+external-product, gadget, bootstrap, keyswitch and packing calls (tests/test_gpu_random_fhe.py).  Prints the failing seeds, if any.
+    python tools/soak_random.py [extra_seeds_per_family] [plans|native|product|chain|wrap|ext|gadget|nativepbs|keyswitch|pack|primepbs]
 `chain`: the fused mul_accumulate chain kernels with batches of more than two rounds of their persistent grids (random
-primes of every class, random sizes / terms / outputs; tests/test_external_product_multitrip.py::run_chain_case)."""
+primes of every class, random sizes / terms / outputs; tests/test_external_product_multitrip.py::run_chain_case).
+`ext` ... `primepbs`: the external-product, gadget, bootstrap, keyswitch and packing calls on the cases of tests/random_cases.py, with
+the comparisons of tests/test_gpu_random_fhe.py, from the first seed the test suite does not run; a tenth of the seeds each when no
+family is named.  A wrong word is a failed seed and the run goes on; a device error ends the run at once: nothing more is launched on a
+GPU that has faulted."""
 import os
 import sys
 
@@ -81,5 +86,34 @@ if only in (None, "wrap"):
         if seed % 20 == 0:
             print("wrap seed", seed, (bits, n, p), flush=True)
     print("wrap done", flush=True)
+import random_cases as rc  # noqa: E402
+from concrete_ntt_amd._lib import DeviceError  # noqa: E402
+
+
+def device_error(e):
+    text = repr(e)
+    return isinstance(e, DeviceError) or (not isinstance(e, AssertionError) and any(
+        t in text for t in ("HIP error", "hipError", "illegal memory access", "out of memory", "HSA_STATUS")))
+
+
+for name in rc.FAMILIES:
+    if only and only != name:
+        continue
+    import test_gpu_random_fhe as fhe
+    for seed in range(rc.SEEDS, rc.SEEDS + (extra if only == name else max(extra // 10, 1))):
+        try:
+            fhe.check(oracle, name, seed)
+        except AssertionError as e:
+            bad += 1
+            print("FAIL", name, seed, repr(e)[:600], flush=True)
+        except BaseException as e:
+            print("ERROR", name, seed, repr(e)[:600], flush=True)
+            if device_error(e):
+                print("device error: stopping, failures so far:", bad, flush=True)
+                sys.exit(2)
+            bad += 1
+        if seed % 20 == 0:
+            print(name, "seed", seed, flush=True)
+    print(name, "done", flush=True)
 print("soak done, failures:", bad)
 sys.exit(1 if bad else 0)
