@@ -86,6 +86,11 @@ def lib():
             "bootstrap_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz,
                                         c_int, c_vp]),
             "pbs_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, c_sz]),
+            # include/cntt_prime_keyswitch.h
+            "keyswitch_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_int, c_vp]),
+            "keyswitch_bootstrap_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, ctypes.c_uint, c_vp, c_int, c_vp, c_sz, c_sz,
+                                                  ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
+            "ks_pbs_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, c_sz]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, p + name)

@@ -200,3 +200,56 @@ class PrimePlan(PbsMixin):
         """lwe_modswitch_batch -> blind_rotate_batch -> sample_extract_batch(index=0) mod p in one call: lwe_in batch*(lwe_dim+1) words,
         lwe_out batch*(glwe_dim*n+1) words; rot_t and the accumulator live in the workspace (None: one allocation per call)."""
         self._bootstrap(lwe_out, lwe_in, lut, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, workspace, lut_per_element)
+
+    # -- LWE keyswitch mod p, and keyswitch + bootstrap in one call (include/cntt_prime_keyswitch.h) -------------------------------------
+    def ks_pbs_workspace_bytes(self, lwe_dim, glwe_dim, levels, batch):
+        """Bytes of workspace keyswitch_bootstrap_batch needs: pbs_workspace_bytes() plus the batch*(lwe_dim+1) keyswitched words,
+        rounded up to 256 bytes."""
+        if min(lwe_dim, glwe_dim, levels, batch) < 0:
+            raise Panic("lwe_dim, glwe_dim, levels and batch must not be negative")
+        return self._fn("ks_pbs_workspace_bytes")(self._h, lwe_dim, glwe_dim, levels, batch)
+
+    def _ksk(self, ksk, where, rows, lwe_dim_out, row_stride):
+        """pointer of a keyswitch key of `rows` rows of row_stride words (None: packed), the last of which may end after its
+        lwe_dim_out + 1 words; returns (pointer, row_stride)"""
+        if row_stride is None:
+            row_stride = lwe_dim_out + 1
+        kp, kc, kw, _ = self._words(ksk)
+        if row_stride < lwe_dim_out + 1:
+            raise Panic("row_stride must be at least lwe_dim_out + 1 words")
+        if kw != where or kc < (((rows - 1) * row_stride + lwe_dim_out + 1) if rows else 0):
+            raise Panic("ksk: lwe_dim_in*levels rows of row_stride words in the memory of the other buffers")
+        return kp, row_stride
+
+    def keyswitch_batch(self, lwe_out, lwe_in, ksk, lwe_dim_in, lwe_dim_out, base_log, levels, row_stride=None):
+        """lwe_out[b][c] = (lwe_in[b][lwe_dim_in] if c == lwe_dim_out) - sum_{i,l} digit_l(lwe_in[b][i]) * ksk[i*levels + l-1][c] mod p,
+        the digits those of gadget_decompose_batch (balanced lift, top digit unmasked): lwe_in batch*(lwe_dim_in+1) words, lwe_out
+        batch*(lwe_dim_out+1) words, ksk lwe_dim_in*levels rows of row_stride words (None: lwe_dim_out+1, packed), row (i, l) an LWE
+        encryption under the output key of s_in[i] * 2^(W - base_log*l) mod p, body last; W = the bit length of p."""
+        ip, ic, where, stream = self._words(lwe_in)
+        op, oc, ow, _ = self._words(lwe_out)
+        if lwe_dim_in < 0 or lwe_dim_out < 0 or levels <= 0 or base_log <= 0 or ic % (lwe_dim_in + 1) or ow != where:
+            raise Panic("lwe_in: batch*(lwe_dim_in+1) words; lwe_out in the same memory; base_log, levels >= 1")
+        batch = ic // (lwe_dim_in + 1)
+        if oc != batch * (lwe_dim_out + 1):
+            raise Panic("lwe_out must hold batch*(lwe_dim_out+1) = %d words" % (batch * (lwe_dim_out + 1)))
+        kp, row_stride = self._ksk(ksk, where, lwe_dim_in * levels, lwe_dim_out, row_stride)
+        check(self._fn("keyswitch_batch")(self._h, op, ip, kp, lwe_dim_in, lwe_dim_out, row_stride, base_log, levels, batch, where, stream))
+
+    def keyswitch_bootstrap_batch(self, lwe_out, lwe_in, ksk, ks_base_log, ks_levels, lut, bsk_ntt, lwe_dim, glwe_dim, base_log, levels,
+                                  workspace=None, lut_per_element=None, row_stride=None):
+        """keyswitch_batch from dimension glwe_dim*n to lwe_dim (digits ks_base_log, ks_levels) followed by bootstrap_batch, in one call
+        and with the words of the two: lwe_in and lwe_out are both batch*(glwe_dim*n+1) words, so the call chains with itself.
+        workspace: None (one allocation per call) or a buffer of ks_pbs_workspace_bytes()."""
+        ip, ic, where, stream = self._words(lwe_in)
+        op, oc, ow, _ = self._words(lwe_out)
+        big = glwe_dim * self._n if glwe_dim >= 0 else -1
+        if lwe_dim < 0 or glwe_dim < 0 or min(levels, base_log, ks_levels, ks_base_log) <= 0 or ic % (big + 1) or ow != where or oc != ic:
+            raise Panic("lwe_in and lwe_out: batch*(glwe_dim*n+1) words each in the same memory; base_log, levels >= 1")
+        batch = ic // (big + 1)
+        kp, row_stride = self._ksk(ksk, where, big * ks_levels, lwe_dim, row_stride)
+        lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
+        key = self._bsk(bsk_ntt, where, lwe_dim, glwe_dim, levels)
+        wp, wb = self._workspace(workspace, where)
+        check(self._fn("keyswitch_bootstrap_batch")(self._h, op, ip, kp, row_stride, ks_base_log, ks_levels, lp, per, key, lwe_dim, glwe_dim,
+                                                    base_log, levels, batch, wp, wb, where, stream))

@@ -22,6 +22,7 @@
 
 #include "cntt.h"
 #include "cntt_ext.h"
+#include "cntt_prime_keyswitch.h"
 #include "cntt_prime_pbs.h"
 
 namespace cntt {
@@ -105,6 +106,20 @@ template <class T> struct PrimeApi;
         }                                                                                                            \
         static size_t pbs_workspace_bytes(const handle *h, size_t ld, size_t gd, unsigned lv, size_t k) {             \
             return cntt_prime##BITS##_pbs_workspace_bytes(h, ld, gd, lv, k);                                          \
+        }                                                                                                            \
+        /* cntt_prime_keyswitch.h */                                                                                 \
+        static int keyswitch_batch(const handle *h, T *o, const T *in, const T *ksk, size_t li, size_t lo, size_t rs, unsigned bl, \
+                                   unsigned lv, size_t k, cntt_mem_t w, void *s) {                                    \
+            return cntt_prime##BITS##_keyswitch_batch(h, o, in, ksk, li, lo, rs, bl, lv, k, w, s);                    \
+        }                                                                                                            \
+        static int keyswitch_bootstrap_batch(const handle *h, T *o, const T *in, const T *ksk, size_t rs, unsigned kbl, unsigned klv, \
+                                             const T *lut, int per, const T *bsk, size_t ld, size_t gd, unsigned bl, unsigned lv,  \
+                                             size_t k, void *ws, size_t wsb, cntt_mem_t w, void *s) {                 \
+            return cntt_prime##BITS##_keyswitch_bootstrap_batch(h, o, in, ksk, rs, kbl, klv, lut, per, bsk, ld, gd, bl, lv, k, ws, wsb, \
+                                                                w, s);                                               \
+        }                                                                                                            \
+        static size_t ks_pbs_workspace_bytes(const handle *h, size_t ld, size_t gd, unsigned lv, size_t k) {          \
+            return cntt_prime##BITS##_ks_pbs_workspace_bytes(h, ld, gd, lv, k);                                       \
         }                                                                                                            \
     };
 CNTT_PRIME_TRAITS(32, uint32_t)
@@ -193,6 +208,22 @@ template <class T> class PrimePlan {
     }
     size_t pbs_workspace_bytes(size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) const {
         return A::pbs_workspace_bytes(h_, lwe_dim, glwe_dim, levels, batch);
+    }
+    // LWE keyswitch mod p (cntt_prime_keyswitch.h) from lwe_dim_in to lwe_dim_out, and keyswitch (glwe_dim * n -> lwe_dim) + bootstrap in
+    // one call
+    void keyswitch_batch(T *lwe_out, const T *lwe_in, const T *ksk, size_t lwe_dim_in, size_t lwe_dim_out, size_t row_stride,
+                         unsigned base_log, unsigned levels, size_t batch, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(A::keyswitch_batch(h_, lwe_out, lwe_in, ksk, lwe_dim_in, lwe_dim_out, row_stride, base_log, levels, batch, where, stream));
+    }
+    size_t ks_pbs_workspace_bytes(size_t lwe_dim, size_t glwe_dim, unsigned levels_bsk, size_t batch) const {
+        return A::ks_pbs_workspace_bytes(h_, lwe_dim, glwe_dim, levels_bsk, batch);
+    }
+    void keyswitch_bootstrap_batch(T *lwe_out, const T *lwe_in, const T *ksk, size_t row_stride, unsigned ks_base_log, unsigned ks_levels,
+                                   const T *lut, bool lut_per_element, const T *bsk_ntt, size_t lwe_dim, size_t glwe_dim,
+                                   unsigned base_log, unsigned levels, size_t batch, void *workspace = nullptr, size_t workspace_bytes = 0,
+                                   cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(A::keyswitch_bootstrap_batch(h_, lwe_out, lwe_in, ksk, row_stride, ks_base_log, ks_levels, lut, lut_per_element ? 1 : 0,
+                                           bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, where, stream));
     }
     const typename A::handle *handle() const { return h_; }
 };
