@@ -91,6 +91,10 @@ def lib():
             "keyswitch_bootstrap_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, ctypes.c_uint, c_vp, c_int, c_vp, c_sz, c_sz,
                                                   ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
             "ks_pbs_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, c_sz]),
+            # include/cntt_prime_pack.h
+            "pack_keyswitch_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int,
+                                             c_vp]),
+            "pack_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, p + name)

@@ -253,3 +253,33 @@ class PrimePlan(PbsMixin):
         wp, wb = self._workspace(workspace, where)
         check(self._fn("keyswitch_bootstrap_batch")(self._h, op, ip, kp, row_stride, ks_base_log, ks_levels, lp, per, key, lwe_dim, glwe_dim,
                                                     base_log, levels, batch, wp, wb, where, stream))
+
+    # -- LWE-to-GLWE packing keyswitch through the NTT mod p (include/cntt_prime_pack.h) -------------------------------------------------
+    def pack_workspace_bytes(self, lwe_dim_in, levels, batch):
+        """Bytes of workspace pack_keyswitch_batch needs: the negated digit polynomials of one chunk of mask words, rounded up to 256
+        bytes."""
+        if min(lwe_dim_in, batch) < 0 or levels <= 0:
+            raise Panic("lwe_dim_in and batch must not be negative, levels >= 1")
+        return self._fn("pack_workspace_bytes")(self._h, lwe_dim_in, levels, batch)
+
+    def pack_keyswitch_batch(self, glwe_out, lwe_in, pksk_ntt, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, workspace=None):
+        """glwe_out[g][q] = (sum_t lwe_in[g][t][lwe_dim_in] X^t if q == glwe_dim) - sum_{i,l} D_{g,i,l} (*) K[i*levels + l-1][q] mod p,
+        D_{g,i,l}[t] = digit_l(lwe_in[g][t][i]) for t < lwe_count, else 0, the digits those of gadget_decompose_batch: lwe_count LWE
+        ciphertexts packed into one GLWE ciphertext whose coefficient t carries message t.  lwe_in: batch*lwe_count*(lwe_dim_in+1)
+        words; glwe_out: batch*(glwe_dim+1) polynomials; pksk_ntt: ONE buffer of lwe_dim_in*levels*(glwe_dim+1) polynomials holding
+        n^-1 * fwd(key) (fwd_batch, then normalize_batch), row (i, l) a GLWE encryption under the output key of the constant
+        s_in[i] * 2^(W - base_log*l) mod p; workspace: None (one allocation per call) or a buffer of pack_workspace_bytes()."""
+        ip, ic, where, stream = self._words(lwe_in)
+        op, oc, ow, _ = self._words(glwe_out)
+        n = self._n
+        if lwe_dim_in < 0 or glwe_dim < 0 or lwe_count <= 0 or levels <= 0 or base_log <= 0 or ic % (lwe_count * (lwe_dim_in + 1)) or ow != where:
+            raise Panic("lwe_in: batch*lwe_count*(lwe_dim_in+1) words; glwe_out in the same memory; lwe_count, base_log, levels >= 1")
+        batch = ic // (lwe_count * (lwe_dim_in + 1))
+        if oc != batch * (glwe_dim + 1) * n:
+            raise Panic("glwe_out must hold batch*(glwe_dim+1) = %d polynomials" % (batch * (glwe_dim + 1)))
+        kp, kc, kw, _ = self._words(pksk_ntt)
+        if kw != where or kc != lwe_dim_in * levels * (glwe_dim + 1) * n:
+            raise Panic("pksk_ntt: lwe_dim_in*levels*(glwe_dim+1) NTT-domain polynomials in the memory of the other buffers")
+        wp, wb = self._workspace(workspace, where)
+        check(self._fn("pack_keyswitch_batch")(self._h, op, ip, kp, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, wp, wb, where,
+                                               stream))

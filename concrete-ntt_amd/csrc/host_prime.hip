@@ -563,3 +563,4 @@ template int external_product_device<uint64_t>(const PrimePlan<uint64_t> *, uint
 // the programmable bootstrap mod p around external_product_device (include/cntt_prime_pbs.h)
 #include "host_prime_pbs.inc"
 #include "host_prime_keyswitch.inc"
+#include "host_prime_pack.inc"

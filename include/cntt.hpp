@@ -23,6 +23,7 @@
 #include "cntt.h"
 #include "cntt_ext.h"
 #include "cntt_prime_keyswitch.h"
+#include "cntt_prime_pack.h"
 #include "cntt_prime_pbs.h"
 
 namespace cntt {
@@ -120,6 +121,14 @@ template <class T> struct PrimeApi;
         }                                                                                                            \
         static size_t ks_pbs_workspace_bytes(const handle *h, size_t ld, size_t gd, unsigned lv, size_t k) {          \
             return cntt_prime##BITS##_ks_pbs_workspace_bytes(h, ld, gd, lv, k);                                       \
+        }                                                                                                            \
+        /* cntt_prime_pack.h */                                                                                      \
+        static int pack_keyswitch_batch(const handle *h, T *o, const T *in, const T *key, size_t li, size_t m, size_t gd, unsigned bl, \
+                                        unsigned lv, size_t k, void *ws, size_t wsb, cntt_mem_t w, void *s) {         \
+            return cntt_prime##BITS##_pack_keyswitch_batch(h, o, in, key, li, m, gd, bl, lv, k, ws, wsb, w, s);       \
+        }                                                                                                            \
+        static size_t pack_workspace_bytes(const handle *h, size_t li, unsigned lv, size_t k) {                       \
+            return cntt_prime##BITS##_pack_workspace_bytes(h, li, lv, k);                                             \
         }                                                                                                            \
     };
 CNTT_PRIME_TRAITS(32, uint32_t)
@@ -224,6 +233,17 @@ template <class T> class PrimePlan {
                                    cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
         check(A::keyswitch_bootstrap_batch(h_, lwe_out, lwe_in, ksk, row_stride, ks_base_log, ks_levels, lut, lut_per_element ? 1 : 0,
                                            bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, where, stream));
+    }
+    // LWE-to-GLWE packing keyswitch through the NTT mod p (cntt_prime_pack.h): lwe_count LWE ciphertexts of dimension lwe_dim_in into one
+    // GLWE; pksk_ntt = n^-1 fwd(key), one buffer
+    size_t pack_workspace_bytes(size_t lwe_dim_in, unsigned levels, size_t batch) const {
+        return A::pack_workspace_bytes(h_, lwe_dim_in, levels, batch);
+    }
+    void pack_keyswitch_batch(T *glwe_out, const T *lwe_in, const T *pksk_ntt, size_t lwe_dim_in, size_t lwe_count, size_t glwe_dim,
+                              unsigned base_log, unsigned levels, size_t batch, void *workspace = nullptr, size_t workspace_bytes = 0,
+                              cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(A::pack_keyswitch_batch(h_, glwe_out, lwe_in, pksk_ntt, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, workspace,
+                                      workspace_bytes, where, stream));
     }
     const typename A::handle *handle() const { return h_; }
 };

@@ -2,12 +2,13 @@
 """Extended run of the seeded random GPU parity sweeps (tests/test_gpu_random.py) over many more seeds than the
 test suite uses: prime plans, native polymul plans, product plans, multi-trip chains, the strict class's wrap zone, and the
 external-product, gadget, bootstrap, keyswitch and packing calls (tests/test_gpu_random_fhe.py).  Prints the failing seeds, if any.
-    python tools/soak_random.py [extra_seeds_per_family] [plans|native|product|chain|wrap|ext|gadget|nativepbs|keyswitch|pack|primepbs]
+    python tools/soak_random.py [extra_seeds_per_family] [plans|native|product|chain|wrap|ext|gadget|nativepbs|keyswitch|pack|primepbs|primepack]
 `chain`: the fused mul_accumulate chain kernels with batches of more than two rounds of their persistent grids (random
 primes of every class, random sizes / terms / outputs; tests/test_external_product_multitrip.py::run_chain_case).
 `ext` ... `primepbs`: the external-product, gadget, bootstrap, keyswitch and packing calls on the cases of tests/random_cases.py, with
 the comparisons of tests/test_gpu_random_fhe.py, from the first seed the test suite does not run; a tenth of the seeds each when no
-family is named.  A wrong word is a failed seed and the run goes on; a device error ends the run at once: nothing more is launched on a
+family is named.  `primepack`: the prime plans' packing keyswitch on the cases of tests/random_prime_pack_cases.py, with the comparisons
+of tests/test_gpu_random_prime_pack.py, in the same way.  A wrong word is a failed seed and the run goes on; a device error ends the run at once: nothing more is launched on a
 GPU that has faulted."""
 import os
 import sys
@@ -96,13 +97,20 @@ def device_error(e):
         t in text for t in ("HIP error", "hipError", "illegal memory access", "out of memory", "HSA_STATUS")))
 
 
-for name in rc.FAMILIES:
+def check_primepack(orc, name, seed):
+    import random_prime_pack_cases as pp
+    import test_gpu_random_prime_pack as tpp
+    tpp.check_primepack(orc, pp.case_primepack(seed))
+
+
+for name in rc.FAMILIES + ("primepack",):
     if only and only != name:
         continue
     import test_gpu_random_fhe as fhe
+    check = check_primepack if name == "primepack" else fhe.check
     for seed in range(rc.SEEDS, rc.SEEDS + (extra if only == name else max(extra // 10, 1))):
         try:
-            fhe.check(oracle, name, seed)
+            check(oracle, name, seed)
         except AssertionError as e:
             bad += 1
             print("FAIL", name, seed, repr(e)[:600], flush=True)
