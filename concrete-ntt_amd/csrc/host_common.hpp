@@ -2,8 +2,9 @@
 // structs behind the C ABI, error reporting, the host-slice staging and the functions that cross unit borders.  Internal, never
 // installed.  Every __global__ template is launched -- and so instantiated -- by exactly ONE unit; the others call the host function
 // that owns the launch, declared here and explicitly instantiated there.  Nothing declared here is exported.
-// pbs_host.hpp, on top of this file, is the host side of the programmable bootstrap as templates over the plan family: host_native_ext.hip
-// and host_prime.hip (through host_prime_pbs.inc) each include it and instantiate it for their plans.
+// pbs_host.hpp, on top of this file, is the host side of the programmable bootstrap as templates over the plan family, and lwe_host.hpp, on
+// top of that, the host side of the keyswitch, keyswitch + bootstrap and packing keyswitch: host_native_ext.hip and host_prime.hip (through
+// its host_prime_*.inc) each include them and instantiate them for their plans.
 #pragma once
 #include <hip/hip_runtime.h>
 

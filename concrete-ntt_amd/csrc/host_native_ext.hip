@@ -1,15 +1,16 @@
 // libcntt_hip.so host side, what is built on the native plans without a counterpart in the reference: the external product
 // (include/cntt_ext.h), rotation / gadget decomposition and the external product on undecomposed polynomials (include/cntt_gadget.h),
 // the programmable bootstrap (include/cntt_pbs.h), the LWE keyswitch and keyswitch + bootstrap (include/cntt_keyswitch.h), the
-// LWE-to-GLWE packing keyswitch (include/cntt_pack.h).
+// LWE-to-GLWE packing keyswitch (include/cntt_pack.h).  The last three are the templates of pbs_host.hpp and lwe_host.hpp, shared with the
+// prime plans: here are the family struct that fits them to the native plans (NativePbs) and the C ABI over them.
 #include <cstdio>
 
 #include "host_common.hpp"
+#include "lwe_host.hpp"
 #include "native_gadget.hpp"
 #include "native_keyswitch.hpp"
 #include "native_pack.hpp"
 #include "native_pbs.hpp"
-#include "pbs_host.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // external product of the native plans (include/cntt_ext.h; no counterpart in the reference)
@@ -190,8 +191,10 @@ static int native_gadget_device(const cntt_native *pl, void *terms, const void *
     });
 }
 
-// What the shared bootstrap pipeline (pbs_host.hpp) needs to know of the native plans: words of 4, 8 or 16 bytes behind void pointers, digits
-// of the whole word, and a key of one residue plane per prime.
+// What the shared host pipelines (pbs_host.hpp, lwe_host.hpp) need to know of the native plans: words of 4, 8 or 16 bytes behind void
+// pointers, digits of the whole word, and a key of one residue plane per prime.  One struct for the bootstrap, the keyswitch and the
+// packing keyswitch (the name is from its first user), so that the combined call runs the bootstrap's own instantiation of the loop.
+#pragma GCC visibility push(hidden)
 struct NativePbs {
     using Plan = cntt_native;
     using Word = void;
@@ -199,7 +202,7 @@ struct NativePbs {
     static size_t word(const cntt_native *pl) { return (size_t)pl->info.word; }
     static int logn(const cntt_native *pl) { return native_logn(pl); }
     static unsigned digit_bits(const cntt_native *pl) { return 8u * (unsigned)pl->info.word; }
-    static constexpr const char *DIGIT_BUDGET_MSG = "base_log * levels = %u * %u exceeds the word width %u";
+    static constexpr const char *DIGIT_BUDGET_MSG = "%sbase_log * %slevels = %u * %u exceeds the word width %u";
     static int check_terms(const cntt_native *pl, size_t glwe_dim, unsigned levels) {
         const size_t nterms = (glwe_dim + 1) * levels;
         if (nterms > pl->max_terms)
@@ -212,9 +215,9 @@ struct NativePbs {
     struct KeyStore {
         const void *plane[10];
     };
-    static int key_check(const cntt_native *pl, Key bsk) {
-        if (!bsk) return fail(CNTT_EINVAL, "bsk_ntt is NULL");
-        return check_key_planes(pl, bsk, "bsk_ntt");
+    static int key_check(const cntt_native *pl, Key key, const char *name) {
+        if (!key) return fail(CNTT_EINVAL, "%s is NULL", name);
+        return check_key_planes(pl, key, name);
     }
     static size_t key_bytes(const cntt_native *pl, size_t polys) { return polys * pl->n * pl->rbytes(); }
     static Key key_in(const cntt_native *pl, Staging &s, Key bsk, size_t bytes, KeyStore &ks) {
@@ -242,7 +245,38 @@ struct NativePbs {
     }
     static constexpr auto gadget = native_gadget_device;   // the two steps of the loop
     static constexpr auto ext_product = native_ext_device;
+
+    // the keyswitch (lwe_host.hpp); these plans have no bound on the key rows
+    static constexpr bool KS_ROWS_GUARD = false;
+    static hipError_t launch_keyswitch(const cntt_native *pl, void *out, const void *in, const void *ksk, size_t lin, size_t lout,
+                                       size_t row_stride, unsigned base_log, unsigned levels, size_t batch, hipStream_t st) {
+        const u128 off = gadget_offset(digit_bits(pl), base_log, levels);
+        return launch_native_keyswitch(pl->info.word, out, in, ksk, (uint64_t)off, (uint64_t)(off >> 64), base_log, levels, lin, lout,
+                                       row_stride, batch, st);
+    }
+
+    // the packing keyswitch (lwe_host.hpp)
+    static size_t pack_chunk_terms(const cntt_native *pl) { return std::min<size_t>(pl->max_terms, CNTT_PACK_TERMS); }
+    static int pack_check_levels(const cntt_native *pl, unsigned levels) {
+        if (levels > pl->max_terms)
+            return fail(CNTT_EINVAL, "levels = %u exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range", levels,
+                        pl->max_terms);
+        return CNTT_OK;
+    }
+    static int pack_check_sizes(const cntt_native *, size_t, size_t, size_t, unsigned, size_t) { return CNTT_OK; }
+    static bool pack_key_overlaps(const void *, size_t, Key, size_t) { return false; }
+    static hipError_t launch_pack_body(const cntt_native *pl, void *out, const void *in, size_t glwe_dim, size_t lin, size_t m, size_t batch,
+                                       unsigned grid, hipStream_t st) {
+        return launch_native_pack_body(pl->info.word, out, in, native_logn(pl), glwe_dim, lin, m, batch, grid, st);
+    }
+    static hipError_t launch_pack_decompose(const cntt_native *pl, void *terms, const void *in, unsigned base_log, unsigned levels, size_t lin,
+                                            size_t m, size_t i0, size_t nw, size_t batch, hipStream_t st) {
+        const u128 off = gadget_offset(digit_bits(pl), base_log, levels);
+        return launch_native_pack_decompose(pl->info.word, terms, in, (uint64_t)off, (uint64_t)(off >> 64), base_log, levels, native_logn(pl),
+                                            lin, m, i0, nw, batch, st);
+    }
 };
+#pragma GCC visibility pop
 
 extern "C" int cntt_native_gadget_decompose_batch(const cntt_native_t *pl, void *terms, const void *polys, const uint32_t *rot,
                                                   size_t npolys, unsigned base_log, unsigned levels, cntt_src_mode_t src_mode, size_t batch,
@@ -366,194 +400,36 @@ extern "C" int cntt_native_bootstrap_batch(const cntt_native_t *pl, void *lwe_ou
 }
 
 // ---------------------------------------------------------------------------------------------
-// LWE keyswitch, and keyswitch + bootstrap in one call (include/cntt_keyswitch.h, native_keyswitch.hpp)
+// LWE keyswitch, and keyswitch + bootstrap in one call (include/cntt_keyswitch.h, native_keyswitch.hpp; host side: lwe_host.hpp)
 // ---------------------------------------------------------------------------------------------
-// the digit and stride checks the two calls share; `pre` = "" or "ks_": how the combined call names the keyswitch's digit arguments
-static int keyswitch_check(const cntt_native *pl, size_t lwe_dim_out, size_t row_stride, unsigned base_log, unsigned levels, const char *pre) {
-    const unsigned wbits = 8u * (unsigned)pl->info.word;
-    if (base_log == 0) return fail(CNTT_EINVAL, "%sbase_log is 0", pre);
-    if (levels == 0) return fail(CNTT_EINVAL, "%slevels is 0", pre);
-    if ((uint64_t)base_log * levels > wbits)
-        return fail(CNTT_EINVAL, "%sbase_log * %slevels = %u * %u exceeds the word width %u", pre, pre, base_log, levels, wbits);
-    if (base_log > 31) return fail(CNTT_EINVAL, "%sbase_log = %u exceeds 31: the keyswitch keeps a digit in one 32-bit register", pre, base_log);
-    if (row_stride < lwe_dim_out + 1)
-        return fail(CNTT_EINVAL, "row_stride = %zu is below lwe_dim_out + 1 = %zu words", row_stride, lwe_dim_out + 1);
-    return CNTT_OK;
-}
-// bytes of a key of `rows` rows: the last row needs its lwe_dim_out + 1 words only
-static size_t ksk_bytes(const cntt_native *pl, size_t rows, size_t lwe_dim_out, size_t row_stride) {
-    return rows ? ((rows - 1) * row_stride + lwe_dim_out + 1) * (size_t)pl->info.word : 0;
-}
-static int native_keyswitch_device(const cntt_native *pl, void *out, const void *in, const void *ksk, size_t lin, size_t lout,
-                                   size_t row_stride, unsigned base_log, unsigned levels, size_t batch, hipStream_t st) {
-    const u128 off = gadget_offset(8u * (unsigned)pl->info.word, base_log, levels);
-    const hipError_t e = launch_native_keyswitch(pl->info.word, out, in, ksk, (uint64_t)off, (uint64_t)(off >> 64), base_log, levels, lin, lout,
-                                                 row_stride, batch, st);
-    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_keyswitch_kernel launch failed: %s", hipGetErrorString(e));
-    return CNTT_OK;
-}
 
 extern "C" int cntt_native_keyswitch_batch(const cntt_native_t *pl, void *lwe_out, const void *lwe_in, const void *ksk, size_t lwe_dim_in,
                                            size_t lwe_dim_out, size_t row_stride, unsigned base_log, unsigned levels, size_t batch,
                                            cntt_mem_t where, void *stream) {
-    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
-    if (int rc = keyswitch_check(pl, lwe_dim_out, row_stride, base_log, levels, "")) return rc;
-    if (batch == 0) return CNTT_OK;
-    if (!lwe_out) return fail(CNTT_EINVAL, "lwe_out is NULL");
-    if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
-    if (lwe_dim_in && !ksk) return fail(CNTT_EINVAL, "ksk is NULL");
-    const size_t w = (size_t)pl->info.word, ob = batch * (lwe_dim_out + 1) * w, ib = batch * (lwe_dim_in + 1) * w;
-    const size_t kb = ksk_bytes(pl, lwe_dim_in * levels, lwe_dim_out, row_stride);
-    if (ranges_overlap(lwe_out, ob, lwe_in, ib)) return fail(CNTT_EINVAL, "lwe_out overlaps lwe_in");
-    if (ranges_overlap(lwe_out, ob, ksk, kb)) return fail(CNTT_EINVAL, "lwe_out overlaps ksk");
-    hipStream_t st = (hipStream_t)stream;
-    if (where == CNTT_MEM_DEVICE)
-        return native_keyswitch_device(pl, lwe_out, lwe_in, ksk, lwe_dim_in, lwe_dim_out, row_stride, base_log, levels, batch, st);
-    Staging s(st);
-    void *dout = s.out(lwe_out, ob);
-    const void *din = s.in(lwe_in, ib), *dk = s.in(ksk, kb);
-    if (int rc = s.status()) return rc;
-    if (int rc = native_keyswitch_device(pl, dout, din, dk, lwe_dim_in, lwe_dim_out, row_stride, base_log, levels, batch, st)) return rc;
-    return s.finish();
+    return keyswitch<NativePbs>(pl, lwe_out, lwe_in, ksk, lwe_dim_in, lwe_dim_out, row_stride, base_log, levels, batch, where, (hipStream_t)stream);
 }
-
-// bytes of the keyswitched ciphertexts, which follow the bootstrap's part of the workspace (cntt_keyswitch.h states the formula)
-static size_t ks_mid_bytes(const cntt_native *pl, size_t lwe_dim, size_t batch) { return batch * (lwe_dim + 1) * (size_t)pl->info.word; }
 extern "C" size_t cntt_native_ks_pbs_workspace_bytes(const cntt_native_t *pl, size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) {
-    return pl ? pbs_sizes<NativePbs>(pl, lwe_dim, glwe_dim, levels, batch).total() + up256(ks_mid_bytes(pl, lwe_dim, batch)) : 0;
+    return ks_pbs_workspace_bytes<NativePbs>(pl, lwe_dim, glwe_dim, levels, batch);
 }
-
 extern "C" int cntt_native_keyswitch_bootstrap_batch(const cntt_native_t *pl, void *lwe_out, const void *lwe_in, const void *ksk,
                                                      size_t row_stride, unsigned ks_base_log, unsigned ks_levels, const void *lut,
                                                      int lut_per_element, const void *const *bsk_ntt, size_t lwe_dim, size_t glwe_dim,
                                                      unsigned base_log, unsigned levels, size_t batch, void *workspace, size_t workspace_bytes,
                                                      cntt_mem_t where, void *stream) {
-    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
-    if (int rc = keyswitch_check(pl, lwe_dim, row_stride, ks_base_log, ks_levels, "ks_")) return rc;
-    const PbsSizes Z = pbs_sizes<NativePbs>(pl, lwe_dim, glwe_dim, levels, batch);
-    const size_t mid = ks_mid_bytes(pl, lwe_dim, batch), need = Z.total() + up256(mid);
-    if (int rc = pbs_check<NativePbs>(pl, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, need)) return rc;
-    if (batch == 0) return CNTT_OK;
-    if (!lwe_out) return fail(CNTT_EINVAL, "lwe_out is NULL");
-    if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
-    if (!lut) return fail(CNTT_EINVAL, "lut is NULL");
-    const size_t big = glwe_dim * pl->n;   // the dimension of both ends
-    if (big && !ksk) return fail(CNTT_EINVAL, "ksk is NULL");
-    const size_t w = (size_t)pl->info.word, eb = batch * (big + 1) * w, kb = ksk_bytes(pl, big * ks_levels, lwe_dim, row_stride);
-    const size_t lb = lut_per_element ? Z.acc : Z.acc / batch;
-    if (ranges_overlap(lwe_out, eb, lwe_in, eb)) return fail(CNTT_EINVAL, "lwe_out overlaps lwe_in");
-    if (ranges_overlap(lwe_out, eb, ksk, kb)) return fail(CNTT_EINVAL, "lwe_out overlaps ksk");
-    if (ranges_overlap(lwe_out, eb, lut, lb)) return fail(CNTT_EINVAL, "lwe_out overlaps lut");
-    if (workspace) {
-        if (ranges_overlap(lwe_out, eb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_out overlaps workspace");
-        if (ranges_overlap(lwe_in, eb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_in overlaps workspace");
-        if (ranges_overlap(ksk, kb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "ksk overlaps workspace");
-        if (ranges_overlap(lut, lb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lut overlaps workspace");
-    }
-    hipStream_t st = (hipStream_t)stream;
-    // keyswitch into the tail of the workspace, bootstrap from there with the head
-    auto run = [&](void *out, const void *in, const void *key, const void *table, const void *const *bsk, char *ws) {
-        void *lwe_mid = ws + Z.total();
-        if (int rc = native_keyswitch_device(pl, lwe_mid, in, key, big, lwe_dim, row_stride, ks_base_log, ks_levels, batch, st)) return rc;
-        return bootstrap_device<NativePbs>(pl, out, lwe_mid, table, lut_per_element != 0, bsk, lwe_dim, glwe_dim, base_log, levels, batch, Z, ws, st);
-    };
-    if (where == CNTT_MEM_DEVICE) {
-        void *ws = workspace;
-        if (!ws) HIP_TRY(hipMallocAsync(&ws, need, st));   // one allocation for the whole call
-        const int rc = run(lwe_out, lwe_in, ksk, lut, bsk_ntt, static_cast<char *>(ws));
-        if (!workspace) (void)hipFreeAsync(ws, st);
-        return rc;
-    }
-    const size_t bb = lwe_dim * (glwe_dim + 1) * levels * (glwe_dim + 1) * pl->n * pl->rbytes();
-    Staging s(st);
-    const void *dkey[10];
-    if (lwe_dim) key_planes_to_device(pl, s, bsk_ntt, bb, dkey);
-    const void *din = s.in(lwe_in, eb), *dk = s.in(ksk, kb), *dlut = s.in(lut, lb);
-    void *dout = s.out(lwe_out, eb), *dws = s.alloc(need);
-    if (int rc = s.status()) return rc;
-    if (int rc = run(dout, din, dk, dlut, dkey, static_cast<char *>(dws))) return rc;
-    return s.finish();
+    return keyswitch_bootstrap<NativePbs>(pl, lwe_out, lwe_in, ksk, row_stride, ks_base_log, ks_levels, lut, lut_per_element, bsk_ntt, lwe_dim,
+                                         glwe_dim, base_log, levels, batch, workspace, workspace_bytes, where, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
-// LWE-to-GLWE packing keyswitch through the NTT (include/cntt_pack.h, native_pack.hpp)
+// LWE-to-GLWE packing keyswitch through the NTT (include/cntt_pack.h, native_pack.hpp; host side: lwe_host.hpp)
 // ---------------------------------------------------------------------------------------------
-// mask words of one external product: C of the header, capped at lin (levels >= 1)
-static size_t pack_chunk(const cntt_native *pl, size_t lin, unsigned levels) {
-    const size_t c = std::max<size_t>(1, std::min<size_t>(pl->max_terms, CNTT_PACK_TERMS) / levels);
-    return std::min(c, lin);
-}
-static size_t pack_terms_bytes(const cntt_native *pl, size_t lin, unsigned levels, size_t batch) {
-    return batch * pack_chunk(pl, lin, levels) * levels * pl->n * (size_t)pl->info.word;
-}
+
 extern "C" size_t cntt_native_pack_workspace_bytes(const cntt_native_t *pl, size_t lwe_dim_in, unsigned levels, size_t batch) {
-    return pl && levels ? up256(pack_terms_bytes(pl, lwe_dim_in, levels, batch)) : 0;
+    return pack_workspace_bytes<NativePbs>(pl, lwe_dim_in, levels, batch);
 }
-
-// out = the body polynomial, then per chunk of mask words the negated digit polynomials into `terms` and the external product
-// accumulating into out.  In place is sound as in blind_rotate_device (pbs_host.hpp): a chunk's terms are complete before its product starts
-// and rewritten only after it (stream order), and the product reads only the terms and the key.
-static int native_pack_device(const cntt_native *pl, void *out, const void *in, const void *const *pksk, size_t lin, size_t m, size_t glwe_dim,
-                              unsigned base_log, unsigned levels, size_t batch, void *terms, hipStream_t st) {
-    const size_t npolys = glwe_dim + 1, n = pl->n, chunk = pack_chunk(pl, lin, levels);
-    const int logn = native_logn(pl);
-    hipError_t e = launch_native_pack_body(pl->info.word, out, in, logn, glwe_dim, lin, m, batch, ew_grid(batch * npolys * n), st);
-    if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_pack_body_kernel launch failed: %s", hipGetErrorString(e));
-    const u128 off = gadget_offset(8u * (unsigned)pl->info.word, base_log, levels);
-    const size_t row = levels * npolys * n * pl->rbytes();   // one mask word's key rows, bytes per plane
-    const int k = pl->info.nprimes;
-    const void *key[10];
-    for (size_t i0 = 0; i0 < lin; i0 += chunk) {
-        const size_t nw = std::min(chunk, lin - i0);
-        for (int j = 0; j < k; ++j) key[j] = static_cast<const char *>(pksk[j]) + i0 * row;
-        e = launch_native_pack_decompose(pl->info.word, terms, in, (uint64_t)off, (uint64_t)(off >> 64), base_log, levels, logn, lin, m, i0, nw,
-                                         batch, st);
-        if (e != hipSuccess) return fail(CNTT_EDEVICE, "native_pack_decompose_kernel launch failed: %s", hipGetErrorString(e));
-        if (int rc = native_ext_device(pl, out, terms, key, nw * levels, npolys, batch, true, st)) return rc;
-    }
-    return CNTT_OK;
-}
-
 extern "C" int cntt_native_pack_keyswitch_batch(const cntt_native_t *pl, void *glwe_out, const void *lwe_in, const void *const *pksk_ntt,
                                                 size_t lwe_dim_in, size_t lwe_count, size_t glwe_dim, unsigned base_log, unsigned levels,
                                                 size_t batch, void *workspace, size_t workspace_bytes, cntt_mem_t where, void *stream) {
-    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
-    if (int rc = gadget_check<NativePbs>(pl, base_log, levels, CNTT_SRC_PLAIN, nullptr)) return rc;
-    if (levels > pl->max_terms)
-        return fail(CNTT_EINVAL, "levels = %u exceeds cntt_native_max_terms() = %zu: the sum would leave the exact CRT range", levels,
-                    pl->max_terms);
-    if (lwe_count == 0 || lwe_count > pl->n)
-        return fail(CNTT_EINVAL, "lwe_count = %zu is not in 1 .. ntt_size = %zu", lwe_count, pl->n);
-    if (glwe_dim + 1 >= ((size_t)1 << 32)) return fail(CNTT_EINVAL, "glwe_dim too large");
-    if (batch == 0) return CNTT_OK;
-    if (!glwe_out) return fail(CNTT_EINVAL, "glwe_out is NULL");
-    if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
-    if (lwe_dim_in) {
-        if (!pksk_ntt) return fail(CNTT_EINVAL, "pksk_ntt is NULL");
-        if (int rc = check_key_planes(pl, pksk_ntt, "pksk_ntt")) return rc;
-    }
-    const size_t n = pl->n, w = (size_t)pl->info.word, ob = batch * (glwe_dim + 1) * n * w, ib = batch * lwe_count * (lwe_dim_in + 1) * w;
-    const size_t need = up256(pack_terms_bytes(pl, lwe_dim_in, levels, batch));
-    if (ranges_overlap(glwe_out, ob, lwe_in, ib)) return fail(CNTT_EINVAL, "glwe_out overlaps lwe_in");
-    if (workspace) {
-        if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
-        if (ranges_overlap(glwe_out, ob, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "glwe_out overlaps workspace");
-        if (ranges_overlap(lwe_in, ib, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_in overlaps workspace");
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (where == CNTT_MEM_DEVICE) {
-        void *terms = workspace;
-        if (!terms && lwe_dim_in) HIP_TRY(hipMallocAsync(&terms, need, st));   // one allocation for the whole call
-        const int rc = native_pack_device(pl, glwe_out, lwe_in, pksk_ntt, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, terms, st);
-        if (!workspace && terms) (void)hipFreeAsync(terms, st);
-        return rc;
-    }
-    Staging s(st);
-    const void *dkey[10];
-    if (lwe_dim_in) key_planes_to_device(pl, s, pksk_ntt, lwe_dim_in * levels * (glwe_dim + 1) * n * pl->rbytes(), dkey);
-    const void *din = s.in(lwe_in, ib);
-    void *dout = s.out(glwe_out, ob), *dterms = s.alloc(need);
-    if (int rc = s.status()) return rc;
-    if (int rc = native_pack_device(pl, dout, din, dkey, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, dterms, st)) return rc;
-    return s.finish();
+    return pack_keyswitch<NativePbs>(pl, glwe_out, lwe_in, pksk_ntt, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, workspace,
+                                      workspace_bytes, where, (hipStream_t)stream);
 }

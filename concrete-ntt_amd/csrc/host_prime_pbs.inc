@@ -62,12 +62,12 @@ template <class T> struct PrimePbs {
     static size_t word(const Plan *) { return sizeof(T); }
     static int logn(const Plan *pl) { return pl->logn; }
     static unsigned digit_bits(const Plan *pl) { return modulus_bits(pl); }
-    static constexpr const char *DIGIT_BUDGET_MSG = "base_log * levels = %u * %u exceeds the bit length %u of the modulus";
+    static constexpr const char *DIGIT_BUDGET_MSG = "%sbase_log * %slevels = %u * %u exceeds the bit length %u of the modulus";
     static int check_terms(const Plan *, size_t, unsigned) { return CNTT_OK; }   // the sums are taken mod p: any number of terms
 
     using Key = const T *;
     struct KeyStore {};
-    static int key_check(const Plan *, Key bsk) { return bsk ? CNTT_OK : fail(CNTT_EINVAL, "bsk_ntt is NULL"); }
+    static int key_check(const Plan *, Key key, const char *name) { return key ? CNTT_OK : fail(CNTT_EINVAL, "%s is NULL", name); }
     static size_t key_bytes(const Plan *pl, size_t polys) { return polys * pl->n * sizeof(T); }
     static Key key_in(const Plan *, Staging &s, Key bsk, size_t bytes, KeyStore &) { return (Key)s.in(bsk, bytes); }
     static Key key_at(const Plan *, Key bsk, size_t offset, KeyStore &) { return bsk + offset / sizeof(T); }

@@ -2,7 +2,7 @@
 // (include/cntt_prime_pbs.h, host_prime.hip): argument checks, the host-slice staging, the workspace layout and the blind rotation loop.
 // Internal, never installed.  Every function here is a template over a family F, one struct of static members per plan family that supplies
 // what the two differ in and nothing else: NativePbs (host_native_ext.hip) and PrimePbs<T> (host_prime_pbs.inc) show the members.
-// keyswitch_bootstrap at the end is the keyswitch + bootstrap call, used by the prime plans (host_prime_keyswitch.inc).
+// lwe_host.hpp, on top of this file, does the same for the keyswitch, the keyswitch + bootstrap call and the packing keyswitch.
 #pragma once
 #include "host_common.hpp"
 
@@ -14,12 +14,12 @@ inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t b
 }
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// the checks every call with digits shares
+// the checks every call with digits shares (DIGIT_BUDGET_MSG takes a prefix for the two names first: lwe_host.hpp has one)
 template <class F> int gadget_check(const typename F::Plan *pl, unsigned base_log, unsigned levels, int mode, const uint32_t *rot) {
     const unsigned wbits = F::digit_bits(pl);
     if (base_log == 0) return fail(CNTT_EINVAL, "base_log is 0");
     if (levels == 0) return fail(CNTT_EINVAL, "levels is 0");
-    if ((uint64_t)base_log * levels > wbits) return fail(CNTT_EINVAL, F::DIGIT_BUDGET_MSG, base_log, levels, wbits);
+    if ((uint64_t)base_log * levels > wbits) return fail(CNTT_EINVAL, F::DIGIT_BUDGET_MSG, "", "", base_log, levels, wbits);
     if (mode != CNTT_SRC_PLAIN && mode != CNTT_SRC_ROTATE && mode != CNTT_SRC_CMUX) return fail(CNTT_EINVAL, "src_mode %d is not a cntt_src_mode_t", mode);
     if (mode != CNTT_SRC_PLAIN && !rot) return fail(CNTT_EINVAL, "rot is NULL and src_mode reads it");
     return CNTT_OK;
@@ -156,7 +156,7 @@ int pbs_check(const typename F::Plan *pl, typename F::Key bsk, size_t lwe_dim, s
     if (int rc = F::check_terms(pl, glwe_dim, levels)) return rc;
     if (batch == 0) return CNTT_OK;
     if (lwe_dim)
-        if (int rc = F::key_check(pl, bsk)) return rc;
+        if (int rc = F::key_check(pl, bsk, "bsk_ntt")) return rc;
     if (workspace)
         if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
     return CNTT_OK;
@@ -254,67 +254,6 @@ int bootstrap(const typename F::Plan *pl, typename F::Word *lwe_out, const typen
     if (int rc = s.status()) return rc;
     if (int rc = bootstrap_device<F>(pl, dout, din, dlut, lut_per_element != 0, dkey, lwe_dim, glwe_dim, base_log, levels, batch, Z, dws, st))
         return rc;
-    return s.finish();
-}
-
-// Keyswitch from dimension k n to lwe_dim, then the bootstrap, in one call.  The family supplies the keyswitch: ks_check (the digit and
-// stride checks, `pre` = how the digit arguments are named), ks_key_bytes and ks_device.  The workspace holds the bootstrap's part
-// (PbsSizes) first and the batch x (lwe_dim + 1) keyswitched ciphertexts behind it.
-template <class F> size_t ks_pbs_workspace_bytes(const typename F::Plan *pl, size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch) {
-    return pl ? pbs_sizes<F>(pl, lwe_dim, glwe_dim, levels, batch).total() + up256(batch * (lwe_dim + 1) * F::word(pl)) : 0;
-}
-
-template <class F>
-int keyswitch_bootstrap(const typename F::Plan *pl, typename F::Word *lwe_out, const typename F::Word *lwe_in, const typename F::Word *ksk,
-                        size_t row_stride, unsigned ks_base_log, unsigned ks_levels, const typename F::Word *lut, int lut_per_element,
-                        typename F::Key bsk, size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels, size_t batch, void *workspace,
-                        size_t workspace_bytes, cntt_mem_t where, hipStream_t st) {
-    using W = typename F::Word;
-    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
-    if (glwe_dim + 1 >= ((size_t)1 << 32)) return fail(CNTT_EINVAL, "glwe_dim too large");   // before it is multiplied (pbs_check's bound)
-    const size_t big = glwe_dim * pl->n;   // the dimension of both ends: below 2^32 n, no wrap
-    if (int rc = F::ks_check(pl, big, lwe_dim, row_stride, ks_base_log, ks_levels, "ks_")) return rc;
-    const PbsSizes Z = pbs_sizes<F>(pl, lwe_dim, glwe_dim, levels, batch);
-    const size_t need = ks_pbs_workspace_bytes<F>(pl, lwe_dim, glwe_dim, levels, batch);
-    if (int rc = pbs_check<F>(pl, bsk, lwe_dim, glwe_dim, base_log, levels, batch, workspace, workspace_bytes, need)) return rc;
-    if (batch == 0) return CNTT_OK;
-    if (!lwe_out) return fail(CNTT_EINVAL, "lwe_out is NULL");
-    if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
-    if (!lut) return fail(CNTT_EINVAL, "lut is NULL");
-    if (big && !ksk) return fail(CNTT_EINVAL, "ksk is NULL");
-    const size_t eb = batch * (big + 1) * F::word(pl), kb = F::ks_key_bytes(pl, big * ks_levels, lwe_dim, row_stride);
-    const size_t lb = lut_per_element ? Z.acc : Z.acc / batch;
-    if (ranges_overlap(lwe_out, eb, lwe_in, eb)) return fail(CNTT_EINVAL, "lwe_out overlaps lwe_in");
-    if (ranges_overlap(lwe_out, eb, ksk, kb)) return fail(CNTT_EINVAL, "lwe_out overlaps ksk");
-    if (ranges_overlap(lwe_out, eb, lut, lb)) return fail(CNTT_EINVAL, "lwe_out overlaps lut");
-    if (workspace) {
-        if (ranges_overlap(lwe_out, eb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_out overlaps workspace");
-        if (ranges_overlap(lwe_in, eb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_in overlaps workspace");
-        if (ranges_overlap(ksk, kb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "ksk overlaps workspace");
-        if (ranges_overlap(lut, lb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lut overlaps workspace");
-    }
-    // keyswitch into the tail of the workspace, bootstrap from there with the head
-    auto run = [&](W *out, const W *in, const W *key, const W *table, typename F::Key bkey, char *ws) {
-        W *lwe_mid = static_cast<W *>(static_cast<void *>(ws + Z.total()));
-        if (int rc = F::ks_device(pl, lwe_mid, in, key, big, lwe_dim, row_stride, ks_base_log, ks_levels, batch, st)) return rc;
-        return bootstrap_device<F>(pl, out, lwe_mid, table, lut_per_element != 0, bkey, lwe_dim, glwe_dim, base_log, levels, batch, Z, ws, st);
-    };
-    if (where == CNTT_MEM_DEVICE) {
-        void *ws = workspace;
-        if (!ws) HIP_TRY(hipMallocAsync(&ws, need, st));   // one allocation for the whole call
-        const int rc = run(lwe_out, lwe_in, ksk, lut, bsk, static_cast<char *>(ws));
-        if (!workspace) (void)hipFreeAsync(ws, st);
-        return rc;
-    }
-    const size_t bb = F::key_bytes(pl, lwe_dim * (glwe_dim + 1) * levels * (glwe_dim + 1));
-    Staging s(st);
-    typename F::KeyStore ks;
-    const typename F::Key dkey = lwe_dim ? F::key_in(pl, s, bsk, bb, ks) : typename F::Key{};
-    const W *din = (const W *)s.in(lwe_in, eb), *dk = (const W *)s.in(ksk, kb), *dlut = (const W *)s.in(lut, lb);
-    W *dout = (W *)s.out(lwe_out, eb);
-    char *dws = (char *)s.alloc(need);
-    if (int rc = s.status()) return rc;
-    if (int rc = run(dout, din, dk, dlut, dkey, dws)) return rc;
     return s.finish();
 }
 

@@ -248,6 +248,21 @@ def test_the_bootstrap_cases_of_the_combined_call_are_refused():
     assert c.untouched()
 
 
+def test_glwe_dim_of_the_combined_call_is_bounded_after_the_keyswitch_checks():
+    """the native order: the keyswitch's digit and stride checks first, glwe_dim with the bootstrap's (no key-row bound here: a dimension
+    past 2^32 key rows gets as far as the bootstrap's term count)"""
+    c = Case()
+
+    def call(glwe_dim, ks_base_log=8, stride=L + 1, ks_levels=3):
+        return cntt.lib().cntt_native_keyswitch_bootstrap_batch(c.plan._h, ptr(c.big_out), ptr(c.big_in), ptr(c.big_ksk), stride, ks_base_log,
+                                                                ks_levels, ptr(c.lut), 0, c.kp(), L, glwe_dim, 8, 2, B, None, 0, 0, None)
+    assert call((1 << 32) - 1) == EINVAL and "glwe_dim too large" in err()
+    assert call((1 << 32) - 1, ks_base_log=0) == EINVAL and "ks_base_log is 0" in err()
+    assert call((1 << 32) - 1, stride=L) == EINVAL and "row_stride" in err()
+    assert call((1 << 32) // N, ks_levels=1) == EINVAL and "cntt_native_max_terms" in err()
+    assert c.untouched()
+
+
 def test_row_stride_below_a_row_is_refused():
     c = Case()
     assert c.ks(stride=LOUT) == EINVAL and "row_stride" in err()

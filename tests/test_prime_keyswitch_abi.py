@@ -290,6 +290,11 @@ def test_combined_call_refuses_every_invalid_argument(bits, p):
         (dict(inp=inside, ws=c.ws), "lwe_in overlaps workspace"),
         (dict(ksk=c.ws.view(c.dtype), ws=c.ws), "ksk overlaps workspace"),
         (dict(lut=inside[:(K + 1) * N], ws=c.ws), "lut overlaps workspace"),
+        # glwe_dim is bounded before it is multiplied into the keyswitch's dimension, so before the keyswitch's digits too; then the rows
+        (dict(glwe_dim=(1 << 32) - 1), "glwe_dim too large"),
+        (dict(glwe_dim=(1 << 32) - 1, ks_base_log=0), "glwe_dim too large"),
+        (dict(glwe_dim=(1 << 32) // N, ks_levels=1), "lwe_dim_in * ks_levels"),
+        (dict(glwe_dim=(1 << 32) // N, ks_levels=1, stride=L), "row_stride"),
     ]
     for kw, word in cases:
         assert c.combined(**kw) == EINVAL, kw
