@@ -34,7 +34,9 @@ __global__ __launch_bounds__(256) void pointwise_kernel(T *__restrict__ a, const
             if constexpr (OP == PW_ADD) va[k] = add_mod<T>(va[k], vb[k], P.p);
         }
     };
-    // two vectors per thread in flight (the loads of the second are issued before the arithmetic of the first)
+    // two vectors per thread in flight (the loads of the second are issued before the arithmetic of the first).  Caller pointers promise
+    // sizeof(T) alignment only (include/cntt.h, "Operands"), less than V's: the casts stand on global_load / store_dwordx4 executing at
+    // 4-byte alignment on gfx950 (tests/test_gpu_footprint.py runs every call one word past a 16-byte boundary)
     auto ld = [](const T *base, size_t i) -> V {
         if constexpr (STREAM) return __builtin_nontemporal_load(reinterpret_cast<const V *>(base) + i);
         else return reinterpret_cast<const V *>(base)[i];

@@ -36,6 +36,32 @@ int fail(int code, const char *fmt, ...);
         if (e_ != hipSuccess) return fail(CNTT_EDEVICE, "%s: %s", #expr, hipGetErrorString(e_));    \
     } while (0)
 
+// The aliasing and alignment contract of the _batch calls (include/cntt.h, "Operands"): every operand aligned to its word, and an
+// operand the call writes disjoint from every other one; read-only operands may coincide.  Pointer comparisons only, before any device
+// call.  The later headers' calls (pbs_host.hpp, lwe_host.hpp) name their pairs one by one with ranges_overlap.
+inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return abytes && bbytes && x < y + bbytes && y < x + abytes;
+}
+struct Operand {
+    const char *name;
+    const void *ptr;
+    size_t bytes, align;
+    bool written;
+};
+inline int check_operands(const Operand *ops, int count) {
+    for (int i = 0; i < count; ++i)
+        if (ops[i].bytes && (uintptr_t)ops[i].ptr % ops[i].align)
+            return fail(CNTT_EINVAL, "%s is not %zu-byte aligned", ops[i].name, ops[i].align);
+    for (int i = 0; i < count; ++i)
+        for (int j = i + 1; j < count; ++j)
+            if ((ops[i].written || ops[j].written) && ranges_overlap(ops[i].ptr, ops[i].bytes, ops[j].ptr, ops[j].bytes)) {
+                const Operand &w = ops[i].written ? ops[i] : ops[j], &o = ops[i].written ? ops[j] : ops[i];
+                return fail(CNTT_EINVAL, "%s overlaps %s", w.name, o.name);
+            }
+    return CNTT_OK;
+}
+
 // Grid of the element-wise kernels (grid-stride loops: any grid is correct): one 256-thread block per 256 work items, NOT capped at
 // a few blocks per CU.  Measured (tools/pw_probe.py, 65536 x 1024 u64): mul_assign_normalize 0.374 -> 0.271 ms (4.3 -> 5.9 TB/s),
 // normalize 0.232 -> 0.178 ms (4.6 -> 6.0 TB/s) against the 2048-block persistent form; split / CRT / Garner kernels -4 ... -7 %.

@@ -389,8 +389,16 @@ static int native_op(const cntt_native *pl, int op, void *value, void *const *re
     const int k = pl->info.nprimes;
     for (int i = 0; i < k; ++i)
         if (!res[i]) return fail(CNTT_EINVAL, "NULL residue buffer");
-    if (where == CNTT_MEM_DEVICE) return native_op_device(pl, op, value, res, batch, st);
     const size_t count = batch * pl->n, vbytes = count * (size_t)pl->info.word, rb = count * pl->rbytes();
+    {   // fwd writes the planes, inv the planes and the value: none of them may overlap another (include/cntt.h, "Operands")
+        static const char *const PLANE[10] = {"residues[0]", "residues[1]", "residues[2]", "residues[3]", "residues[4]",
+                                              "residues[5]", "residues[6]", "residues[7]", "residues[8]", "residues[9]"};
+        Operand ops[11];
+        ops[0] = {"value", value, vbytes, (size_t)pl->info.word, op == 2};
+        for (int i = 0; i < k; ++i) ops[1 + i] = {PLANE[i], res[i], rb, pl->rbytes(), true};
+        if (int rc = check_operands(ops, 1 + k)) return rc;
+    }
+    if (where == CNTT_MEM_DEVICE) return native_op_device(pl, op, value, res, batch, st);
     // fwd reads the value and writes the residues; inv reads the residues and writes the value AND the (inverse-transformed)
     // residues: src/native64.rs:1010-1014
     Staging s(st);
@@ -559,8 +567,10 @@ extern "C" int cntt_native_negacyclic_polymul_batch(const cntt_native_t *pl, voi
     if (!pl || !prod || !lhs || !rhs) return fail(CNTT_EINVAL, "NULL argument");
     if (batch == 0) return CNTT_OK;
     hipStream_t st = (hipStream_t)stream;
+    const size_t vbytes = batch * pl->n * (size_t)pl->info.word, word = (size_t)pl->info.word;
+    const Operand ops[3] = {{"prod", prod, vbytes, word, true}, {"lhs", lhs, vbytes, word, false}, {"rhs", rhs, vbytes, word, false}};
+    if (int rc = check_operands(ops, 3)) return rc;
     if (where == CNTT_MEM_DEVICE) return native_polymul_device(pl, prod, lhs, rhs, batch, st);
-    const size_t vbytes = batch * pl->n * (size_t)pl->info.word;
     Staging s(st);
     void *dp = s.out(prod, vbytes);
     const void *dl = s.in(lhs, vbytes), *dr = s.in(rhs, vbytes);

@@ -406,8 +406,10 @@ static int external_product(const PrimePlan<T> *pl, T *out, const T *terms, cons
     if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
     if (batch == 0 || nout == 0) return CNTT_OK;
     if (!out || (nterms && (!terms || !key))) return fail(CNTT_EINVAL, "NULL buffer");
-    if (where == CNTT_MEM_DEVICE) return external_product_device<T>(pl, out, terms, key, nterms, nout, batch, accumulate != 0, st);
     const size_t n = pl->n, ob = batch * nout * n * sizeof(T), tb = batch * nterms * n * sizeof(T), kb = nterms * nout * n * sizeof(T);
+    const Operand ops[3] = {{"out", out, ob, sizeof(T), true}, {"terms", terms, tb, sizeof(T), false}, {"key_ntt", key, kb, sizeof(T), false}};
+    if (int rc = check_operands(ops, 3)) return rc;
+    if (where == CNTT_MEM_DEVICE) return external_product_device<T>(pl, out, terms, key, nterms, nout, batch, accumulate != 0, st);
     Staging s(st);
     T *dout = (T *)(accumulate ? s.inout(out, ob) : s.out(out, ob));
     const T *dt = (const T *)s.in(terms, tb), *dk = (const T *)s.in(key, kb);
@@ -423,6 +425,13 @@ static int prime_op(const PrimePlan<T> *pl, int op, T *a, const T *b, const T *c
     if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
     if (count == 0) return CNTT_OK;
     if (!a || ((op == 2 || op == 5) && !b) || (op == 4 && (!b || !c))) return fail(CNTT_EINVAL, "NULL buffer");
+    {   // the written operand first; lhs and rhs of mul_accumulate are read only and may be one buffer (include/cntt.h, "Operands")
+        static const char *const NAMES[6][3] = {{"bufs"}, {"bufs"}, {"lhs", "rhs"}, {"values"}, {"acc", "lhs", "rhs"}, {"lhs", "rhs_ntt"}};
+        const Operand ops[3] = {{NAMES[op][0], a, count * sizeof(T), sizeof(T), true},
+                                {NAMES[op][1], b, b ? count * sizeof(T) : 0, sizeof(T), false},
+                                {NAMES[op][2], c, c ? count * sizeof(T) : 0, sizeof(T), false}};
+        if (int rc = check_operands(ops, 3)) return rc;
+    }
     auto run = [&](T *da, const T *db, const T *dc) -> int {
         switch (op) {
         case 0: return ntt_device<T>(pl, da, batch, false, st);

@@ -295,6 +295,13 @@ static int product_op(const cntt_product *pl, int op, uint64_t *a, uint64_t *b, 
     const size_t std_words = batch * pl->n, dom_words = batch * pl->domain_len();
     const size_t aw = op == 1 ? std_words : dom_words, bw = op == 0 ? std_words : dom_words;
     if ((!a && aw) || (op != 3 && !b && bw) || (op == 4 && !c && dom_words)) return fail(CNTT_EINVAL, "NULL buffer");
+    {   // inv writes both of its buffers; lhs and rhs of mul_accumulate are read only and may be one buffer (include/cntt.h, "Operands")
+        static const char *const NAMES[5][3] = {{"ntt", "standard"}, {"standard", "ntt"}, {"lhs", "rhs"}, {"values"}, {"acc", "lhs", "rhs"}};
+        const Operand ops[3] = {{NAMES[op][0], a, aw * 8, 8, true},
+                                {NAMES[op][1], b, op == 3 ? 0 : bw * 8, 8, op == 1},
+                                {NAMES[op][2], c, op == 4 ? dom_words * 8 : 0, 8, false}};
+        if (int rc = check_operands(ops, 3)) return rc;
+    }
     auto run = [&](uint64_t *da, uint64_t *db, const uint64_t *dc) -> int {
         switch (op) {
         case 0: return product_fwd_device(pl, da, db, batch, mode != 0, bound, st);
@@ -384,9 +391,11 @@ extern "C" int cntt_product_external_product_batch(const cntt_product_t *pl, uin
     if (batch * std::max(nterms, nout) * n >= ((size_t)1 << 40)) return fail(CNTT_EINVAL, "batch too large");
     hipStream_t st = (hipStream_t)stream;
     const bool bounded = fwd_mode == CNTT_FWD_BOUNDED, accumulate = inv_mode == CNTT_INV_ACCUMULATE;
+    const size_t ob = batch * nout * n * 8, tb = batch * nterms * n * 8, kb = nterms * nout * dl * 8;
+    const Operand ops[3] = {{"out", out, ob, 8, true}, {"terms", terms, tb, 8, false}, {"key_ntt", key_ntt, kb, 8, false}};
+    if (int rc = check_operands(ops, 3)) return rc;
     if (where == CNTT_MEM_DEVICE)
         return product_external_product_device(pl, out, terms, key_ntt, nterms, nout, batch, bounded, bound, accumulate, st);
-    const size_t ob = batch * nout * n * 8, tb = batch * nterms * n * 8, kb = nterms * nout * dl * 8;
     Staging s(st);
     uint64_t *dout = (uint64_t *)(accumulate ? s.inout(out, ob) : s.out(out, ob));
     const uint64_t *dt = (const uint64_t *)s.in(terms, tb), *dk = (const uint64_t *)s.in(key_ntt, kb);

@@ -8,10 +8,6 @@
 
 #pragma GCC visibility push(hidden)
 
-inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return abytes && bbytes && x < y + bbytes && y < x + abytes;
-}
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // the checks every call with digits shares (DIGIT_BUDGET_MSG takes a prefix for the two names first: lwe_host.hpp has one)

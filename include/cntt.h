@@ -29,6 +29,25 @@
  *     base + b * n), in place, resident in device memory (CNTT_MEM_DEVICE) or in host memory
  *     (CNTT_MEM_HOST: staged through the device), enqueued on `stream` (a hipStream_t, NULL = default
  *     stream).  Device-resident calls return after enqueueing; they never synchronise.
+ *   - Operands of the _batch calls (and of the host-slice calls on top of them):
+ *       footprint  a call writes the words of its written operands and nothing else -- batch * n words of a transform, a
+ *                  pointwise call or a product, batch * nout * n of an external product, batch * n residues per plane of the
+ *                  native calls, batch * ntt_domain_len words of the product plan's NTT domain -- and not one word before or
+ *                  after them: buffers may be carved back to back out of one allocation.
+ *       aliasing   the operands a call only reads (rhs, rhs_ntt, lhs and rhs of mul_accumulate, lhs and rhs of
+ *                  negacyclic_polymul, terms, key_ntt, standard of product fwd, value of native fwd) may be the same buffer or
+ *                  overlap each other: mul_accumulate_batch(acc, x, x) and negacyclic_polymul_batch(prod, a, a) square, as the
+ *                  reference's shared borrows allow.  An operand the call writes (bufs, values, lhs of mul_assign_normalize and
+ *                  mul_ntt, acc, out, prod, ntt of product fwd, standard AND ntt of product inv, every residue plane of native
+ *                  fwd / inv and value of native inv) may not overlap any other operand of the call, the other residue planes
+ *                  included: CNTT_EINVAL "<written> overlaps <other>", before any device call.  The reference's &mut borrows
+ *                  rule the same calls out at compile time.
+ *       alignment  a pointer is aligned to its word and needs no more: 4 bytes for u32 words and residues, 8 for u64 (a Rust
+ *                  &mut [u64] promises as much), 16 for the u128 words of the native128 kinds; product::Plan buffers are u64
+ *                  words, their u32 residue planes included.  The kernels' 16-byte vector accesses to caller memory are plain
+ *                  global loads and stores, which gfx950 executes at 4-byte alignment.  A pointer below its word's alignment
+ *                  is CNTT_EINVAL "<operand> is not N-byte aligned".  Workspaces (cntt_pbs.h and later headers) are 16-byte
+ *                  aligned as those headers say.
  */
 #ifndef CNTT_H
 #define CNTT_H

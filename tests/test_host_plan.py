@@ -214,3 +214,119 @@ def test_c_examples_run_on_gpu():
     for name in ("mul_poly_prime", "mul_poly_native", "readme_example"):
         r = subprocess.run([os.path.join(ROOT, "examples", name)], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0 and "Success!" in r.stdout, (name, r.returncode, r.stdout, r.stderr)
+
+
+# ---- the aliasing and alignment contract of the core _batch calls (include/cntt.h, "Operands") ----------------------------------------------
+# Refusals are pointer comparisons made before any device call, so they are CNTT_EINVAL with or without a GPU and leave every buffer as it
+# was; a permitted call goes on to the device and returns CNTT_OK with one and CNTT_EDEVICE without -- never CNTT_EINVAL.  The permitted
+# calls run last (`later`): with a GPU they compute.
+EINVAL, HOST = _lib.EINVAL, _lib.MEM_HOST
+
+
+def _ptr(a):
+    return a.ctypes.data
+
+
+def _err():
+    return _lib.last_error()
+
+
+@pytest.mark.parametrize("bits,p", [(64, 4611686018427322369), (32, 1062862849)])
+def test_prime_batch_overlaps_are_refused(bits, p):
+    n, B, later = 32, 3, []
+    L, pl = cntt.lib(), _mod(bits).Plan.try_new(32, p)
+    f = lambda name: getattr(L, "cntt_prime%d_%s" % (bits, name))
+    big = np.full(64 * n, 7, dtype=pl.dtype)
+    before = big.copy()
+    a, near, far, far2 = big[:B * n], big[n:n + B * n], big[8 * n:8 * n + B * n], big[16 * n:16 * n + B * n]
+    for name, second in (("mul_assign_normalize_batch", "rhs"), ("mul_ntt_batch", "rhs_ntt")):
+        assert f(name)(pl._h, _ptr(a), _ptr(near), B, HOST, None) == EINVAL and "lhs overlaps " + second in _err()
+        assert f(name)(pl._h, _ptr(a), _ptr(a), B, HOST, None) == EINVAL and "lhs overlaps " + second in _err()
+        later.append(lambda name=name: f(name)(pl._h, _ptr(a), _ptr(big[B * n:]), B, HOST, None))      # right behind it: no overlap
+    assert f("mul_accumulate_batch")(pl._h, _ptr(a), _ptr(near), _ptr(far), B, HOST, None) == EINVAL and "acc overlaps lhs" in _err()
+    assert f("mul_accumulate_batch")(pl._h, _ptr(a), _ptr(far), _ptr(near), B, HOST, None) == EINVAL and "acc overlaps rhs" in _err()
+    # lhs and rhs are read only: the same buffer, or overlapping ones, are permitted (mul_accumulate(acc, x, x), as the reference allows)
+    later.append(lambda: f("mul_accumulate_batch")(pl._h, _ptr(a), _ptr(far), _ptr(far), B, HOST, None))
+    later.append(lambda: f("mul_accumulate_batch")(pl._h, _ptr(a), _ptr(far), _ptr(big[9 * n:]), B, HOST, None))
+    J, O = 2, 2
+    out, terms, key = big[:B * O * n], big[20 * n:20 * n + B * J * n], big[40 * n:40 * n + J * O * n]
+    ext = f("external_product_batch")
+    assert ext(pl._h, _ptr(out), _ptr(big[B * O * n - 1:]), _ptr(key), J, O, B, 0, HOST, None) == EINVAL and "out overlaps terms" in _err()
+    assert ext(pl._h, _ptr(out), _ptr(terms), _ptr(big[n:]), J, O, B, 1, HOST, None) == EINVAL and "out overlaps key_ntt" in _err()
+    later.append(lambda: ext(pl._h, _ptr(out), _ptr(terms), _ptr(terms), J, O, B, 0, HOST, None))   # terms and key_ntt: both read only
+    # nterms = 0: terms and key_ntt are not read and may be anything
+    later.append(lambda: ext(pl._h, _ptr(out), _ptr(out), _ptr(out), 0, O, B, 1, HOST, None))
+    # below the word's alignment
+    raw = np.zeros(B * n * pl.dtype().itemsize + 16, dtype=np.uint8)
+    off = (bits // 16 - raw.ctypes.data) % 16          # an address that is half a word past a 16-byte boundary
+    assert f("fwd_batch")(pl._h, raw.ctypes.data + off, B, HOST, None) == EINVAL and "bufs is not %d-byte aligned" % (bits // 8) in _err()
+    assert f("normalize_batch")(pl._h, raw.ctypes.data + off, B, HOST, None) == EINVAL and "values is not" in _err()
+    assert np.array_equal(big, before)                      # a refused call touches nothing
+    assert all(call() != EINVAL for call in later)
+
+
+def test_native_batch_overlaps_are_refused():
+    from concrete_ntt_amd import native64, native128
+    n, B, later = 32, 2, []
+    L, pl = cntt.lib(), native64.Plan32.try_new(32)
+    k = pl.NPRIMES
+    val = np.full(16 * n, 5, dtype=np.uint64)
+    res = np.full(64 * n, 9, dtype=np.uint32)
+    vb, rb = val.copy(), res.copy()
+    planes = [res[i * B * n:(i + 1) * B * n] for i in range(k)]
+    arr = lambda ps: (ctypes.c_void_p * k)(*[_ptr(q) for q in ps])
+    for fn in (L.cntt_native_fwd_batch, L.cntt_native_inv_batch):
+        later.append(lambda fn=fn: fn(pl._h, _ptr(val), arr(planes), B, HOST, None))
+        bad = list(planes)
+        bad[3] = res[2 * B * n + 1:2 * B * n + 1 + B * n]          # plane 3 one word into plane 2
+        assert fn(pl._h, _ptr(val), arr(bad), B, HOST, None) == EINVAL and "residues[2] overlaps residues[3]" in _err()
+        bad = list(planes)
+        bad[0] = val[:B * n // 2].view(np.uint32)                  # plane 0 on top of the value
+        assert fn(pl._h, _ptr(val), arr(bad), B, HOST, None) == EINVAL and "overlaps" in _err() and "value" in _err()
+    assert "value overlaps residues[0]" in _err()                  # inv writes both; fwd, which only reads the value, names the plane first
+    bad = list(planes)
+    bad[0] = val[:B * n // 2].view(np.uint32)
+    assert L.cntt_native_fwd_batch(pl._h, _ptr(val), arr(bad), B, HOST, None) == EINVAL and "residues[0] overlaps value" in _err()
+    a, b, c = val[:B * n], val[4 * n:4 * n + B * n], val[8 * n:8 * n + B * n]
+    mul = L.cntt_native_negacyclic_polymul_batch
+    assert mul(pl._h, _ptr(a), _ptr(val[n:]), _ptr(c), B, HOST, None) == EINVAL and "prod overlaps lhs" in _err()
+    assert mul(pl._h, _ptr(a), _ptr(b), _ptr(a), B, HOST, None) == EINVAL and "prod overlaps rhs" in _err()
+    later.append(lambda: mul(pl._h, _ptr(a), _ptr(b), _ptr(b), B, HOST, None))      # negacyclic_polymul(prod, a, a): permitted
+    # u128 words are 16-byte aligned
+    p128 = native128.Plan32.try_new(32)
+    raw = np.zeros(3 * (n * 16) + 32, dtype=np.uint8)
+    base = raw.ctypes.data + (-raw.ctypes.data) % 16
+    q = [base + 8, base + 16 + n * 16, base + 16 + 2 * n * 16]
+    assert mul(p128._h, q[0], q[1], q[2], 1, HOST, None) == EINVAL and "prod is not 16-byte aligned" in _err()
+    assert np.array_equal(val, vb) and np.array_equal(res, rb)   # a refused call touches nothing
+    assert all(call() != EINVAL for call in later)
+
+
+def test_product_batch_overlaps_are_refused(oracle):
+    from concrete_ntt_amd import product
+    n, B, later = 32, 2, []
+    lp = oracle.largest_prime_in_arithmetic_progression64
+    p0 = lp(64, 1, 0, 2**30)
+    primes = [lp(64, 1, 0, p0 - 1), p0]
+    pl = product.Plan.try_new(n, primes[0] * primes[1], primes)
+    L, dl = cntt.lib(), pl.ntt_domain_len()
+    big = np.full(64 * n, 3, dtype=np.uint64)
+    before = big.copy()
+    ntt, std = big[:B * dl], big[16 * n:16 * n + B * n]
+    assert L.cntt_product_fwd_batch(pl._h, _ptr(ntt), _ptr(big[B * dl - 1:]), B, 0, 0, HOST, None) == EINVAL and "ntt overlaps standard" in _err()
+    later.append(lambda: L.cntt_product_fwd_batch(pl._h, _ptr(ntt), _ptr(std), B, 0, 0, HOST, None))
+    for mode in (0, 1):   # inv writes both of its buffers
+        assert L.cntt_product_inv_batch(pl._h, _ptr(big[1:]), _ptr(ntt), B, mode, HOST, None) == EINVAL and "standard overlaps ntt" in _err()
+    a, b, c = ntt, big[20 * n:20 * n + B * dl], big[40 * n:40 * n + B * dl]
+    assert L.cntt_product_mul_assign_normalize_batch(pl._h, _ptr(a), _ptr(a), B, HOST, None) == EINVAL and "lhs overlaps rhs" in _err()
+    assert L.cntt_product_mul_accumulate_batch(pl._h, _ptr(a), _ptr(big[1:]), _ptr(c), B, HOST, None) == EINVAL and "acc overlaps lhs" in _err()
+    assert L.cntt_product_mul_accumulate_batch(pl._h, _ptr(a), _ptr(b), _ptr(big[1:]), B, HOST, None) == EINVAL and "acc overlaps rhs" in _err()
+    later.append(lambda: L.cntt_product_mul_accumulate_batch(pl._h, _ptr(a), _ptr(b), _ptr(b), B, HOST, None))
+    J, O = 2, 2
+    out, terms, key = big[:B * O * n], big[20 * n:20 * n + B * J * n], big[40 * n:40 * n + J * O * dl]
+    ext = L.cntt_product_external_product_batch
+    assert ext(pl._h, _ptr(out), _ptr(big[n:]), _ptr(key), J, O, B, 0, 0, 0, HOST, None) == EINVAL and "out overlaps terms" in _err()
+    assert ext(pl._h, _ptr(out), _ptr(terms), _ptr(big[n:]), J, O, B, 0, 0, 1, HOST, None) == EINVAL and "out overlaps key_ntt" in _err()
+    later.append(lambda: ext(pl._h, _ptr(out), _ptr(terms), _ptr(terms), J, O, B, 0, 0, 0, HOST, None))
+    assert np.array_equal(big, before)                      # a refused call touches nothing
+    assert all(call() != EINVAL for call in later)
