@@ -601,6 +601,25 @@ template <class T, int LOGN, bool SUB> constexpr int plain_fam() { return (sizeo
 // vector-memory wait sits inside the compute phase (twiddles come from LDS / scalar loads), so HBM
 // streaming overlaps the VALU-bound passes instead of alternating with them.
 // -------------------------------------------------------------------------------------------------
+// How a persistent walk of `grid` workgroups x PPB polynomials is cut up (computed on the host, walk_args()): `full` complete rounds
+// of the grid, tile (t * grid + blockIdx.x) on trip t, then `rem` < grid * PPB leftover polynomials.
+//   split = 0: the leftovers go out tile by tile, PPB polynomials to each of the first ceil(rem / PPB) workgroups
+//              (`tile += gridDim.x` until the tiles run out);
+//   split = 1: wavefront by wavefront in the order "wave w of workgroup g", g fastest, so that every CU gets floor or ceil of
+//              rem / grid of them on distinct SIMDs (waves 0 ... 3 of a workgroup before wave 4) instead of a quarter of the CUs
+//              running a full tile next to idle ones.  A wavefront without a leftover polynomial skips the round: no loads, no LDS
+//              traffic, no stores.  Only where a polynomial lives in one wavefront (WAVE_PRIVATE: no s_barrier inside the tile
+//              body, so the waves of a workgroup may run different trip counts); the other shapes ignore the flag.
+// Either way every polynomial is transformed exactly once by the same code: the words written do not depend on the flag.
+struct WalkArgs {
+    uint32_t full, rem, split;
+};
+static __host__ __device__ inline WalkArgs walk_args(uint32_t nsub, uint32_t grid, uint32_t ppb, bool split) {
+    const uint32_t round = grid * ppb;
+    if (round == 0) return WalkArgs{0u, 0u, 0u};
+    return WalkArgs{nsub / round, nsub % round, split ? 1u : 0u};
+}
+
 template <class T, int LOGN, bool INV, int CLS, int WPB, int FAM = 0>
 struct NttWp : NttKernel<T, LOGN, INV, CLS, false, FAM> {
     using B = NttKernel<T, LOGN, INV, CLS, false, FAM>;
@@ -621,6 +640,30 @@ struct NttWp : NttKernel<T, LOGN, INV, CLS, false, FAM> {
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         }
+    }
+
+    // The walk of this wavefront (WAVE_PRIVATE) / workgroup (WalkArgs above): `trips` tiles, the first W.full of them the
+    // workgroup's tiles of the complete rounds, then at most one whose first polynomial is `lbase`.  A thread's polynomial is
+    // always (first polynomial of the tile) + threadIdx.x / TPP, so the leftover wavefront `unit` of the split walk gets the
+    // virtual tile that puts its own polynomials at index unit * PPW.  `step`: polynomials per round of the grid.  All three are
+    // pinned to scalar registers (readfirstlane: free where the value already is one): the tile base feeds the SGPR operand of the
+    // asynchronous loads, and a trip count the compiler takes for divergent would turn the tile loop into an exec-masked one.
+    static __device__ __forceinline__ void walk_plan(const WalkArgs &W, uint32_t &trips, uint32_t &lbase, uint32_t &step) {
+        step = __builtin_amdgcn_readfirstlane(gridDim.x * PPB);
+        const uint32_t r0 = W.full * step;
+        trips = W.full + (blockIdx.x * PPB < W.rem ? 1u : 0u);
+        lbase = r0 + blockIdx.x * PPB;
+        if constexpr (B::WAVE_PRIVATE) {
+            if (W.split) {   // (testing switch walk_split; the barrier shapes have no such branch)
+                constexpr uint32_t PPW = 64 / TPP;   // polynomials per wavefront
+                const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+                const uint32_t unit = wave * (step / PPB) + blockIdx.x;
+                trips = W.full + (unit * PPW < W.rem ? 1u : 0u);
+                lbase = r0 + (unit - wave) * PPW;
+            }
+        }
+        trips = __builtin_amdgcn_readfirstlane(trips);
+        lbase = __builtin_amdgcn_readfirstlane(lbase);
     }
 
 
@@ -656,7 +699,8 @@ struct NttWp : NttKernel<T, LOGN, INV, CLS, false, FAM> {
     // thread-dependent twiddles are read from the table in global memory (L2) inside the passes.
     template <bool USE_IMG = true, int TWC_IMG = 0>
     static __device__ __forceinline__ void run(T *__restrict__ data, const TwPair<T> *__restrict__ tw,
-                                               const ModParams<T> &P, uint32_t nsub, T *lds_all, TwPair<T> *img) {
+                                               const ModParams<T> &P, uint32_t nsub, const WalkArgs &W, T *lds_all,
+                                               TwPair<T> *img) {
         if constexpr (USE_IMG) {
             B::fill_image(img, tw);
             __syncthreads();
@@ -669,32 +713,33 @@ struct NttWp : NttKernel<T, LOGN, INV, CLS, false, FAM> {
         constexpr uint32_t RML = S::RMASK[NPASS - 1], CML = FULL & ~RML;
         constexpr uint32_t CMIO = FULL & ~IO_RM;
         const uint32_t ebase0 = pdep<CM0>(tid), ebaseL = pdep<CML>(tid), ebaseIO = pdep<CMIO>(tid);
-        const uint32_t ntiles = (nsub + PPB - 1) / PPB;
         // byte offset of this thread's first vector inside a tile of PPB polynomials (IO layout)
         const uint32_t voffIO = ((pl << LOGN) + ebaseIO) * (uint32_t)sizeof(T);
         T r[E];
 #pragma unroll
         for (int j = 0; j < E; ++j) r[j] = 0;
-        uint32_t tile = blockIdx.x;
+        uint32_t trips, lbase, step;
+        walk_plan(W, trips, lbase, step);
+        uint32_t base = W.full ? blockIdx.x * PPB : lbase;   // first polynomial of the current tile
         // The first tile takes the same asynchronous path as every later one: plain C++ loads here leave hipcc's vmcnt
         // model with loads in flight at the loop header, and the waits it then places INSIDE the loop drain the next
         // tile's prefetch right after it was issued on every later iteration (no overlap of HBM and butterflies;
         // tests/test_async_load_guard.py now measures the distance between every prefetch and its retiring wait).
-        if (tile < ntiles) {
-            const uint32_t last = nsub - 1u - tile * PPB;   // ragged tail: clamp to the last polynomial (in range)
+        if (trips) {
+            const uint32_t last = nsub - 1u - base;   // ragged tail: clamp to the last polynomial (in range)
             const uint32_t pl0 = pl < last ? pl : last;
             typename B::AsyncVec v0[E / B::MAXV];
-            B::template gather_async_rt<IO_RM>(v0, (const T *)(data + (((size_t)tile * PPB) << LOGN)),
+            B::template gather_async_rt<IO_RM>(v0, (const T *)(data + ((size_t)base << LOGN)),
                                                ((pl0 << LOGN) + ebaseIO) * (uint32_t)sizeof(T), nt);
             B::template wait_async<0>(v0);
             B::unpack_async(r, v0);
         }
         constexpr int NST = E / B::template vec_elems<IO_RM>();  // store instructions per tile (younger than the prefetch)
-        for (; tile < ntiles; tile += gridDim.x) {
-            const uint32_t sub = tile * PPB + pl;
-            const uint32_t tnext = tile + gridDim.x;
-            const bool more = tnext < ntiles;  // workgroup-uniform
-            T *tbase = data + (((size_t)tile * PPB) << LOGN);
+        for (uint32_t t = 0; t < trips; ++t) {
+            const uint32_t sub = base + pl;
+            const uint32_t bnext = t + 1u < W.full ? base + step : lbase;
+            const bool more = t + 1u < trips;  // wave-uniform (workgroup-uniform in the shapes with a barrier)
+            T *tbase = data + ((size_t)base << LOGN);
             // In the shapes compiled for 128 VGPRs every address of the tile body (layout offsets, twiddle offsets) is
             // recomputed per tile from an opaque copy of the thread index: left to itself hipcc hoists all of them out
             // of the tile loop and then spills the lot.
@@ -707,9 +752,9 @@ struct NttWp : NttKernel<T, LOGN, INV, CLS, false, FAM> {
             typename B::AsyncVec vn[E / B::MAXV];
             if (more) {
                 // ragged tail: lanes of polynomials past the end re-read the last polynomial (harmless, in range)
-                const uint32_t last = nsub - 1u - tnext * PPB;
+                const uint32_t last = nsub - 1u - bnext;
                 const uint32_t pln = pl < last ? pl : last;
-                B::template gather_async_rt<IO_RM>(vn, (const T *)(data + (((size_t)tnext * PPB) << LOGN)),
+                B::template gather_async_rt<IO_RM>(vn, (const T *)(data + ((size_t)bnext << LOGN)),
                                                    ((pln << LOGN) + ebIO) * (uint32_t)sizeof(T), nt);
             }
 #pragma unroll
@@ -735,17 +780,18 @@ struct NttWp : NttKernel<T, LOGN, INV, CLS, false, FAM> {
                 B::template wait_async<NST>(vn);
                 B::unpack_async(r, vn);
             }
+            base = bnext;
         }
     }
 };
 
 template <class T, int LOGN, bool INV, int CLS, int WPB, int WPW>
 __global__ __launch_bounds__(WPB, WPW) void ntt_kernel_wp(T *__restrict__ data, const TwPair<T> *__restrict__ tw,
-                                                      const ModParams<T> P, uint32_t nsub) {
+                                                      const ModParams<T> P, uint32_t nsub, const WalkArgs W) {
     using K = NttWp<T, LOGN, INV, CLS, WPB>;
     __shared__ __attribute__((aligned(16))) T lds[(size_t)K::PPB * K::B::LDS_WORDS_1];
     __shared__ __attribute__((aligned(16))) TwPair<T> img[K::B::IMG_ENTRIES];
-    K::run(data, tw, P, nsub, lds, img);
+    K::run(data, tw, P, nsub, W, lds, img);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -770,8 +816,8 @@ struct MulWp {
 
     static __device__ __forceinline__ void run(T *__restrict__ lhs, const T *__restrict__ rhs_ntt,
                                                const TwPair<T> *__restrict__ twf, const TwPair<T> *__restrict__ twi,
-                                               const ModParams<T> &P, uint32_t nsub, T *lds_all, TwPair<T> *imgf,
-                                               TwPair<T> *imgi) {
+                                               const ModParams<T> &P, uint32_t nsub, const WalkArgs &W, T *lds_all,
+                                               TwPair<T> *imgf, TwPair<T> *imgi) {
         FB::fill_image(imgf, twf);
         IB::fill_image(imgi, twi);
         __syncthreads();
@@ -781,32 +827,33 @@ struct MulWp {
         T *lds = lds_all + (size_t)pl * FB::LDS_WORDS_1;
         constexpr uint32_t CM0 = FULL & ~RM0, CMM = FULL & ~RMM, CML = FULL & ~RML, CMIO = FULL & ~IO_RM;
         const uint32_t ebase0 = pdep<CM0>(tid), ebaseM = pdep<CMM>(tid), ebaseL = pdep<CML>(tid), ebaseIO = pdep<CMIO>(tid);
-        const uint32_t ntiles = (nsub + PPB - 1) / PPB;
         const uint32_t voffIO = ((pl << LOGN) + ebaseIO) * (uint32_t)sizeof(T);
         T r[E];
 #pragma unroll
         for (int j = 0; j < E; ++j) r[j] = 0;
-        uint32_t tile = blockIdx.x;
-        if (tile < ntiles) {  // asynchronous like every later tile (see NttWp::run)
-            const uint32_t last = nsub - 1u - tile * PPB;
+        uint32_t trips, lbase, step;   // the walk of this wavefront: NttWp::walk_plan
+        F::walk_plan(W, trips, lbase, step);
+        uint32_t base = W.full ? blockIdx.x * PPB : lbase;
+        if (trips) {  // asynchronous like every later tile (see NttWp::run)
+            const uint32_t last = nsub - 1u - base;
             const uint32_t pl0 = pl < last ? pl : last;
             typename FB::AsyncVec v0[E / FB::MAXV];
-            FB::template gather_async<IO_RM>(v0, (const T *)(lhs + (((size_t)tile * PPB) << LOGN)),
+            FB::template gather_async<IO_RM>(v0, (const T *)(lhs + ((size_t)base << LOGN)),
                                              ((pl0 << LOGN) + ebaseIO) * (uint32_t)sizeof(T));
             FB::template wait_async<0>(v0);
             FB::unpack_async(r, v0);
         }
         constexpr int NST = E / FB::template vec_elems<IO_RM>();
-        for (; tile < ntiles; tile += gridDim.x) {
-            const uint32_t sub = tile * PPB + pl;
-            const uint32_t tnext = tile + gridDim.x;
-            const bool more = tnext < ntiles;
-            T *tbase = lhs + (((size_t)tile * PPB) << LOGN);
+        for (uint32_t t = 0; t < trips; ++t) {
+            const uint32_t sub = base + pl;
+            const uint32_t bnext = t + 1u < W.full ? base + step : lbase;
+            const bool more = t + 1u < trips;
+            T *tbase = lhs + ((size_t)base << LOGN);
             typename FB::AsyncVec vn[E / FB::MAXV];
             if (more) {
-                const uint32_t last = nsub - 1u - tnext * PPB;
+                const uint32_t last = nsub - 1u - bnext;
                 const uint32_t pln = pl < last ? pl : last;
-                FB::template gather_async<IO_RM>(vn, (const T *)(lhs + (((size_t)tnext * PPB) << LOGN)),
+                FB::template gather_async<IO_RM>(vn, (const T *)(lhs + ((size_t)bnext << LOGN)),
                                                  ((pln << LOGN) + ebaseIO) * (uint32_t)sizeof(T));
             }
 #pragma unroll
@@ -821,10 +868,10 @@ struct MulWp {
             F::template pass<0, false, true, mul_fwd_fin<T, CLS>()>(r, lds, tid, twf, imgf, P);
             {
                 // clamped polynomial index for the reads of a ragged tail
-                const uint32_t lastc = nsub - 1u - tile * PPB;
+                const uint32_t lastc = nsub - 1u - base;
                 const uint32_t plc = pl < lastc ? pl : lastc;
                 T b[E];
-                FB::template gather_tile<RMM>(b, rhs_ntt + (((size_t)tile * PPB) << LOGN),
+                FB::template gather_tile<RMM>(b, rhs_ntt + ((size_t)base << LOGN),
                                               ((plc << LOGN) + ebaseM) * (uint32_t)sizeof(T));
 #pragma unroll
                 for (int j = 0; j < E; ++j) r[j] = mul_fused<T, CLS>(r[j], b[j], P);  // 1/N: inside the last inverse stage
@@ -843,6 +890,7 @@ struct MulWp {
                 FB::template wait_async<NST>(vn);
                 FB::unpack_async(r, vn);
             }
+            base = bnext;
         }
     }
 };
@@ -851,12 +899,12 @@ template <class T, int LOGN, int CLS, int WPB, int WPW>
 __global__ __launch_bounds__(WPB, WPW) void mul_kernel_wp(T *__restrict__ lhs, const T *__restrict__ rhs_ntt,
                                                       const TwPair<T> *__restrict__ twf,
                                                       const TwPair<T> *__restrict__ twi, const ModParams<T> P,
-                                                      uint32_t nsub) {
+                                                      uint32_t nsub, const WalkArgs W) {
     using K = MulWp<T, LOGN, CLS, WPB>;
     __shared__ __attribute__((aligned(16))) T lds[(size_t)K::PPB * K::FB::LDS_WORDS_1];
     __shared__ __attribute__((aligned(16))) TwPair<T> imgf[K::FB::IMG_ENTRIES];
     __shared__ __attribute__((aligned(16))) TwPair<T> imgi[K::IB::IMG_ENTRIES];
-    K::run(lhs, rhs_ntt, twf, twi, P, nsub, lds, imgf, imgi);
+    K::run(lhs, rhs_ntt, twf, twi, P, nsub, W, lds, imgf, imgi);
 }
 
 // The same fused product for the sizes that have no LDS twiddle image (32-bit words, N = 8192 ... 32768): one polynomial per

@@ -23,9 +23,11 @@ enum DebugSwitch : int {
     DBG_PLAN52_VIA32,   // 1 (default): negacyclic_polymul of the Plan52 native kinds runs the Plan32 whole-product kernel; 0: composed on 50-bit primes
     DBG_NATIVE_EXT,     // 1 (default): fused external-product kernel of the native Plan32 kinds (native_ext.hpp); 0: composed pipeline
     DBG_NATIVE_GADGET,  // 0 (default): external product on undecomposed polynomials = decompose, then the external product; 1: the fused kernel (native_gadget.hpp), measured slower
+    DBG_WALK_SPLIT,     // 1 (default): the persistent walks of wave-private polynomials (ntt_kernel_wp / mul_kernel_wp, TPP <= 64) hand the leftovers of the last round out one wavefront at a time over all CUs; 0: tile by tile
     DBG_COUNT
 };
 int debug_switch(DebugSwitch key);
+inline bool walk_split_enabled() { return debug_switch(DBG_WALK_SPLIT) != 0; }
 }  // namespace cntt
 
 namespace cntt {

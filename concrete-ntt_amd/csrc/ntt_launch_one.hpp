@@ -87,8 +87,9 @@ static hipError_t launch_one(T *data, const TwPair<T> *tw, const ModParams<T> &P
         const uint32_t ntiles = (nsub + W::PPB - 1) / W::PPB;
         uint32_t grid = (uint32_t)num_cus() * BPC;
         if (grid > ntiles) grid = ntiles;
+        const WalkArgs WA = walk_args(nsub, grid, W::PPB, walk_split_enabled());
         hipLaunchKernelGGL((ntt_kernel_wp<T, LOGN, INV, CLS, WP_BLOCK, BPC>), dim3(grid), dim3(WP_BLOCK), 0, stream, data,
-                           tw, P, nsub);
+                           tw, P, nsub, WA);
     } else {
         const uint32_t grid = (nsub + K::PPB - 1) / K::PPB;
         hipLaunchKernelGGL((ntt_kernel<T, LOGN, INV, CLS, SUB, plain_fam<T, LOGN, SUB>()>), dim3(grid), dim3(K::BLOCK), 0, stream, data,

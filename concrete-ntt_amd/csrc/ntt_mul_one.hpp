@@ -42,8 +42,10 @@ static hipError_t mul_one(T *lhs, const T *rhs, const TwPair<T> *twf, const TwPa
     const uint32_t ntiles = (nsub + K::PPB - 1) / K::PPB;
     uint32_t grid = (uint32_t)mul_num_cus() * SH::PER_CU;
     if (grid > ntiles) grid = ntiles;
+    // how the walk ends: the leftovers of the last round spread over all CUs one wavefront at a time (WalkArgs, ntt_kernel.hpp)
+    const WalkArgs W = walk_args(nsub, grid, K::PPB, walk_split_enabled());
     hipLaunchKernelGGL((mul_kernel_wp<T, LOGN, CLS, SH::BLOCK, SH::WAVES_PER_SIMD>), dim3(grid), dim3(SH::BLOCK), 0, stream,
-                       lhs, rhs, twf, twi, P, nsub);
+                       lhs, rhs, twf, twi, P, nsub, W);
     return hipGetLastError();
 }
 

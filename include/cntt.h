@@ -115,6 +115,9 @@ int cntt_shard_bounds(size_t batch, int world, int rank, size_t *begin, size_t *
 /*   "native_ext"        1     cntt_native_external_product_batch (cntt_ext.h) through the fused kernel; 0: the composed pipeline     */
 /*   "native_gadget"     0     cntt_native_external_product_decomposed_batch (cntt_ext.h): decompose, then                            */
 /*                             cntt_native_external_product_batch; 1: the fused kernel (measured slower, kept for A/B runs)           */
+/*   "walk_split"        1     persistent walks of polynomials that live in one wavefront (ntt_kernel_wp / mul_kernel_wp, n <= 1024    */
+/*                             for 64-bit words): the leftovers of the last round go out one wavefront at a time over all CUs;        */
+/*                             0: tile by tile to the first workgroups                                                                */
 /* value -1 restores a switch's default; key "reset" restores all.  Process-wide, thread-safe (atomics); the two class switches are    */
 /* recorded in the plan at creation (cntt_prime*_plan_info().arith_class reports the class in use), the others are read per call.      */
 /* ------------------------------------------------------------------------------------- */

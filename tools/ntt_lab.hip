@@ -116,7 +116,7 @@ template <bool INV, int WPB, int WPW, int TWC = 0> __global__ __launch_bounds__(
     __shared__ __attribute__((aligned(16))) TwPair<uint64_t> img[K::B::IMG_ENTRIES];
     LabStamp st;
     st.begin();
-    K::template run<true, TWC>(data, tw, P, nsub, lds, img);
+    K::template run<true, TWC>(data, tw, P, nsub, walk_args(nsub, gridDim.x, K::PPB, true), lds, img);
     st.end();
 }
 
@@ -161,7 +161,8 @@ template <bool INV> static void product_kernel(const char *name) {  // what cntt
     uint32_t grid = 256u * 3u;
     if (grid > ntiles) grid = ntiles;
     timeit(name, [&] {
-        hipLaunchKernelGGL((ntt_kernel_wp<uint64_t, 10, INV, LAB_CLS, 256, 3>), dim3(grid), dim3(256), 0, 0, g_data, g_tw, g_P, BATCH);
+        hipLaunchKernelGGL((ntt_kernel_wp<uint64_t, 10, INV, LAB_CLS, 256, 3>), dim3(grid), dim3(256), 0, 0, g_data, g_tw, g_P, BATCH,
+                           walk_args(BATCH, grid, W::PPB, true));
     });
 }
 template <bool INV> static void alu_only(const char *name) {
@@ -193,7 +194,8 @@ template <bool INV> static bool check_wp(const std::vector<uint64_t> &src, uint3
     (void)hipMemcpy(b, src.data(), bytes, hipMemcpyHostToDevice);
     using K0 = NttKernel<uint64_t, 10, INV, LAB_CLS, false>;
     hipLaunchKernelGGL((ntt_kernel<uint64_t, 10, INV, LAB_CLS, false>), dim3((batch + K0::PPB - 1) / K0::PPB), dim3(K0::BLOCK), 0, 0, a, g_tw, g_P, batch, 0u);
-    hipLaunchKernelGGL((ntt_kernel_wp<uint64_t, 10, INV, LAB_CLS, 256, 3>), dim3(grid), dim3(256), 0, 0, b, g_tw, g_P, batch);
+    hipLaunchKernelGGL((ntt_kernel_wp<uint64_t, 10, INV, LAB_CLS, 256, 3>), dim3(grid), dim3(256), 0, 0, b, g_tw, g_P, batch,
+                       walk_args(batch, grid, NttWp<uint64_t, 10, INV, LAB_CLS, 256>::PPB, true));
     std::vector<uint64_t> ha((size_t)batch * 1024), hb((size_t)batch * 1024);
     (void)hipMemcpy(ha.data(), a, bytes, hipMemcpyDeviceToHost);
     (void)hipMemcpy(hb.data(), b, bytes, hipMemcpyDeviceToHost);
