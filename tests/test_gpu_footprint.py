@@ -21,7 +21,9 @@ every device case here: with a count that is a multiple of the vector width the 
 writes the first band word.
 
 The later headers (cntt_ext.h, cntt_gadget.h, cntt_pbs.h, cntt_prime_pbs.h): one small case per call at the end of this file, the
-caller's workspace a written slice of the arena with bands of its own."""
+caller's workspace a written slice of the arena with bands of its own.  The calls on LWE ciphertexts (cntt_keyswitch.h,
+cntt_prime_keyswitch.h, cntt_pack.h, cntt_prime_pack.h) follow in tests/test_gpu_footprint_lwe.py, which takes guard, guard_both, Family,
+_dev and batches_of from here."""
 import numpy as np
 import pytest
 
