@@ -143,6 +143,8 @@ template <class T> struct DeviceTables {
     // plans whose LDS-resident transforms run in a 64-bit-only class: the same twiddles in that class's form --
     // CLS_FP / CLS_FP51: (c, c / p) doubles, c centred in (-p/2, p/2];  CLS_PM64: plain residues;  CLS_FPW: c as one double
     TwPair<T> *fwd_fp = nullptr, *inv_fp = nullptr;
+    // psi^m 2^(2B) mod p for m < n (prime_multibit.hpp): built by the plan's first multi-bit call on the device, nullptr until then
+    T *mono = nullptr;
 };
 template <class T> struct DeviceCache;   // per-device replicas of the tables (host_prime.hip)
 

@@ -18,6 +18,7 @@ template <class T> struct DeviceCache {
             (void)hipFree(kv.second.inv);
             (void)hipFree(kv.second.fwd_fp);
             (void)hipFree(kv.second.inv_fp);
+            (void)hipFree(kv.second.mono);
             (void)hipSetDevice(cur);
         }
     }
@@ -573,3 +574,5 @@ template int external_product_device<uint64_t>(const PrimePlan<uint64_t> *, uint
 #include "host_prime_pbs.inc"
 #include "host_prime_keyswitch.inc"
 #include "host_prime_pack.inc"
+// the multi-bit bootstrap mod p (include/cntt_prime_multibit.h)
+#include "host_prime_multibit.inc"

@@ -23,6 +23,7 @@
 #include "cntt.h"
 #include "cntt_ext.h"
 #include "cntt_prime_keyswitch.h"
+#include "cntt_prime_multibit.h"
 #include "cntt_prime_pack.h"
 #include "cntt_prime_pbs.h"
 
@@ -129,6 +130,24 @@ template <class T> struct PrimeApi;
         }                                                                                                            \
         static size_t pack_workspace_bytes(const handle *h, size_t li, unsigned lv, size_t k) {                       \
             return cntt_prime##BITS##_pack_workspace_bytes(h, li, lv, k);                                             \
+        }                                                                                                            \
+        /* cntt_prime_multibit.h */                                                                                  \
+        static int multibit_accumulate_batch(const handle *h, T *o, const T *t, const uint32_t *r, const T *key, size_t nt, size_t no, \
+                                             unsigned g, size_t k, cntt_mem_t w, void *s) {                           \
+            return cntt_prime##BITS##_multibit_accumulate_batch(h, o, t, r, key, nt, no, g, k, w, s);                 \
+        }                                                                                                            \
+        static int multibit_blind_rotate_batch(const handle *h, T *a, const T *lut, int per, const uint32_t *r, const T *key, size_t ld, \
+                                               size_t gd, unsigned bl, unsigned lv, unsigned g, size_t k, void *ws, size_t wsb,     \
+                                               cntt_mem_t w, void *s) {                                               \
+            return cntt_prime##BITS##_multibit_blind_rotate_batch(h, a, lut, per, r, key, ld, gd, bl, lv, g, k, ws, wsb, w, s); \
+        }                                                                                                            \
+        static int multibit_bootstrap_batch(const handle *h, T *o, const T *in, const T *lut, int per, const T *key, size_t ld, size_t gd, \
+                                            unsigned bl, unsigned lv, unsigned g, size_t k, void *ws, size_t wsb, cntt_mem_t w,       \
+                                            void *s) {                                                                \
+            return cntt_prime##BITS##_multibit_bootstrap_batch(h, o, in, lut, per, key, ld, gd, bl, lv, g, k, ws, wsb, w, s); \
+        }                                                                                                            \
+        static size_t multibit_pbs_workspace_bytes(const handle *h, size_t ld, size_t gd, unsigned lv, unsigned g, size_t k) { \
+            return cntt_prime##BITS##_multibit_pbs_workspace_bytes(h, ld, gd, lv, g, k);                              \
         }                                                                                                            \
     };
 CNTT_PRIME_TRAITS(32, uint32_t)
@@ -244,6 +263,29 @@ template <class T> class PrimePlan {
                               cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
         check(A::pack_keyswitch_batch(h_, glwe_out, lwe_in, pksk_ntt, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, workspace,
                                       workspace_bytes, where, stream));
+    }
+    // multi-bit blind rotation and bootstrap mod p (cntt_prime_multibit.h): groups of `grouping` mask words, one bundled external product
+    // each; bsk_mb = n^-1 fwd(key), one buffer of (lwe_dim / grouping) * 2^grouping GGSW ciphertexts
+    size_t multibit_pbs_workspace_bytes(size_t lwe_dim, size_t glwe_dim, unsigned levels, unsigned grouping, size_t batch) const {
+        return A::multibit_pbs_workspace_bytes(h_, lwe_dim, glwe_dim, levels, grouping, batch);
+    }
+    void multibit_accumulate_batch(T *out_ntt, const T *terms_ntt, const uint32_t *rot_rows, const T *key_group, size_t nterms, size_t nout,
+                                   unsigned grouping, size_t batch, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
+        check(A::multibit_accumulate_batch(h_, out_ntt, terms_ntt, rot_rows, key_group, nterms, nout, grouping, batch, where, stream));
+    }
+    void multibit_blind_rotate_batch(T *acc, const T *lut, bool lut_per_element, const uint32_t *rot_t, const T *bsk_mb, size_t lwe_dim,
+                                     size_t glwe_dim, unsigned base_log, unsigned levels, unsigned grouping, size_t batch,
+                                     void *workspace = nullptr, size_t workspace_bytes = 0, cntt_mem_t where = CNTT_MEM_DEVICE,
+                                     void *stream = nullptr) const {
+        check(A::multibit_blind_rotate_batch(h_, acc, lut, lut_per_element ? 1 : 0, rot_t, bsk_mb, lwe_dim, glwe_dim, base_log, levels,
+                                             grouping, batch, workspace, workspace_bytes, where, stream));
+    }
+    void multibit_bootstrap_batch(T *lwe_out, const T *lwe_in, const T *lut, bool lut_per_element, const T *bsk_mb, size_t lwe_dim,
+                                  size_t glwe_dim, unsigned base_log, unsigned levels, unsigned grouping, size_t batch,
+                                  void *workspace = nullptr, size_t workspace_bytes = 0, cntt_mem_t where = CNTT_MEM_DEVICE,
+                                  void *stream = nullptr) const {
+        check(A::multibit_bootstrap_batch(h_, lwe_out, lwe_in, lut, lut_per_element ? 1 : 0, bsk_mb, lwe_dim, glwe_dim, base_log, levels,
+                                          grouping, batch, workspace, workspace_bytes, where, stream));
     }
     const typename A::handle *handle() const { return h_; }
 };
