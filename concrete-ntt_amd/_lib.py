@@ -150,6 +150,14 @@ def lib():
                                                      c_int, c_vp]),
         "cntt_native_pack_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
         "cntt_prime_multibit_grid": (ctypes.c_uint, [c_sz]),
+        # include/cntt_multibit.h
+        "cntt_native_multibit_grid": (ctypes.c_uint, [c_sz]),
+        "cntt_native_multibit_accumulate_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, c_sz, c_int, c_vp]),
+        "cntt_native_multibit_blind_rotate_batch": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint,
+                                                            ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
+        "cntt_native_multibit_bootstrap_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint,
+                                                         ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
+        "cntt_native_multibit_pbs_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz]),
         "cntt_product_plan_new": (c_int, [c_sz, c_u64, c_vp, c_sz, c_vp]),
         "cntt_product_plan_clone": (c_vp, [c_vp]),
         "cntt_product_plan_free": (None, [c_vp]),

@@ -318,6 +318,93 @@ class NativePlan(PbsMixin):
         check(lib().cntt_native_pack_keyswitch_batch(self._h, op, ip, keys, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, wp, wb,
                                                      where, stream))
 
+    # -- multi-bit blind rotation and bootstrap (include/cntt_multibit.h): Plan32 kinds --------------------------------------------------
+    def multibit_pbs_workspace_bytes(self, lwe_dim, glwe_dim, levels, grouping, batch):
+        """Bytes of workspace multibit_bootstrap_batch needs (digits + term planes + output planes + rot_t + accumulator, each 256-byte
+        aligned); enough for multibit_blind_rotate_batch too.  0 for a Plan52 kind."""
+        if min(lwe_dim, glwe_dim, levels, grouping, batch) < 0:
+            raise Panic("lwe_dim, glwe_dim, levels, grouping and batch must not be negative")
+        return lib().cntt_native_multibit_pbs_workspace_bytes(self._h, lwe_dim, glwe_dim, levels, grouping, batch)
+
+    def _planes(self, planes, where, count, what):
+        """NPRIMES buffers of `count` residues each (count None: not checked) -> the pointer array of the C call"""
+        if len(planes) != self.NPRIMES:
+            raise Panic("expected %d %s residue buffers" % (self.NPRIMES, what))
+        ptrs = []
+        for r in planes:
+            ptr, c, esz, w, _ = buffer_info(r)
+            if esz != self.RES or w != where or (count is not None and c != count):
+                raise Panic("%s residue buffers: %s residues each in the memory of the other buffers" % (what, count))
+            ptrs.append(ptr)
+        return (ctypes.c_void_p * self.NPRIMES)(*ptrs)
+
+    def multibit_accumulate_batch(self, out_residues, terms_residues, rot_rows, key_residues, nterms, nout, grouping):
+        """Per residue prime i: out[i][b][o][c] = n^-1 sum_{t < 2^grouping} fwd_i(X^e_t(b))[c] * sum_j terms[i][b][j][c] * key[i][t][j][o][c]
+        mod P_i; e_t(b) = the sum of rot_rows[q*batch + b] over the set bits q of t, mod 2n.  inv_batch on out_residues then gives the
+        coefficient-domain words.  out_residues: NPRIMES buffers of batch*nout residue polynomials (written only); terms_residues:
+        batch*nterms each; key_residues: 2^grouping*nterms*nout each; rot_rows: grouping*batch uint32."""
+        n = self._n
+        if nout == 0:   # the header: nout == 0 does nothing
+            return
+        _, oc, _, where, stream = buffer_info(out_residues[0]) if len(out_residues) else (None, 0, 0, _lib.MEM_HOST, None)
+        if nout < 0 or nterms < 0 or grouping < 0 or oc % (nout * n):
+            raise Panic("out_residues: batch*nout residue polynomials per prime")
+        batch = oc // (nout * n)
+        outs = self._planes(out_residues, where, oc, "out")
+        terms = self._planes(terms_residues, where, batch * nterms * n, "terms")
+        keys = self._planes(key_residues, where, ((nterms * nout) << grouping) * n if 1 <= grouping <= 4 else None, "key")
+        rp, rc_ = self._rot(rot_rows, where, "rot_rows")
+        if 1 <= grouping <= 4 and rc_ != grouping * batch:
+            raise Panic("rot_rows: grouping*batch uint32")
+        check(lib().cntt_native_multibit_accumulate_batch(self._h, outs, terms, rp, keys, nterms, nout, grouping, batch, where, stream))
+
+    def _bsk_mb(self, bsk_mb, where, lwe_dim, glwe_dim, levels, grouping):
+        # (a grouping the C call refuses is left to it: it names the argument)
+        want = None
+        if 1 <= grouping <= 4 and lwe_dim % grouping == 0:
+            want = ((lwe_dim // grouping) * (glwe_dim + 1) * levels * (glwe_dim + 1) << grouping) * self._n
+        return self._planes(bsk_mb, where, want, "bsk_mb")
+
+    def multibit_blind_rotate_batch(self, acc, lut, rot_t, bsk_mb, lwe_dim, glwe_dim, base_log, levels, grouping, workspace=None,
+                                    lut_per_element=None):
+        """acc[b] = X^rot_t[lwe_dim][b] * lut, then for each group r of `grouping` mask words: acc[b] = sum_t X^e_t ExtProd(bsk_mb[r][t],
+        acc[b]) mod 2^w -- the words of gadget_decompose_batch(mode="plain"), fwd_batch, multibit_accumulate_batch and inv_batch per
+        group.  bsk_mb: NPRIMES buffers of (lwe_dim/grouping)*2^grouping*(glwe_dim+1)*levels*(glwe_dim+1) residue polynomials as
+        fwd_batch writes them, key (r, t) the GGSW of prod_{i in t} s_{r*grouping+i} * prod_{i not in t} (1 - s_{r*grouping+i}).  The
+        rest as blind_rotate_batch; workspace: None or a buffer of multibit_pbs_workspace_bytes()."""
+        ap, ac, where, stream = self._words(acc)
+        n = self._n
+        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or grouping < 0 or ac % ((glwe_dim + 1) * n):
+            raise Panic("acc: batch*(glwe_dim+1) polynomials; base_log, levels >= 1")
+        batch = ac // ((glwe_dim + 1) * n)
+        rp, rc_ = self._rot(rot_t, where, "rot_t")
+        if rc_ != (lwe_dim + 1) * batch:
+            raise Panic("rot_t: (lwe_dim+1)*batch uint32 in the memory of acc")
+        lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
+        key = self._bsk_mb(bsk_mb, where, lwe_dim, glwe_dim, levels, grouping)
+        wp, wb = self._workspace(workspace, where)
+        check(lib().cntt_native_multibit_blind_rotate_batch(self._h, ap, lp, per, rp, key, lwe_dim, glwe_dim, base_log, levels, grouping,
+                                                            batch, wp, wb, where, stream))
+
+    def multibit_bootstrap_batch(self, lwe_out, lwe_in, lut, bsk_mb, lwe_dim, glwe_dim, base_log, levels, grouping, workspace=None,
+                                 lut_per_element=None):
+        """lwe_modswitch_batch -> multibit_blind_rotate_batch -> sample_extract_batch(index=0) mod 2^w in one call: lwe_in
+        batch*(lwe_dim+1) words, lwe_out batch*(glwe_dim*n+1) words; rot_t and the accumulator live in the workspace (None: one
+        allocation per call)."""
+        ip, ic, where, stream = self._words(lwe_in)
+        op, oc, ow, _ = self._words(lwe_out)
+        n = self._n
+        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or grouping < 0 or ic % (lwe_dim + 1) or ow != where:
+            raise Panic("lwe_in: batch*(lwe_dim+1) words; lwe_out in the same memory; base_log, levels >= 1")
+        batch = ic // (lwe_dim + 1)
+        if oc != batch * (glwe_dim * n + 1):
+            raise Panic("lwe_out must hold batch*(glwe_dim*n+1) = %d words" % (batch * (glwe_dim * n + 1)))
+        lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
+        key = self._bsk_mb(bsk_mb, where, lwe_dim, glwe_dim, levels, grouping)
+        wp, wb = self._workspace(workspace, where)
+        check(lib().cntt_native_multibit_bootstrap_batch(self._h, op, ip, lp, per, key, lwe_dim, glwe_dim, base_log, levels, grouping,
+                                                         batch, wp, wb, where, stream))
+
 
 def _make(kind, nprimes, word, res, binary, doc):
     return type("Plan", (NativePlan,), {"KIND": kind, "NPRIMES": nprimes, "WORD": word, "RES": res,

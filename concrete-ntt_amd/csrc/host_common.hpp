@@ -248,6 +248,9 @@ int external_product_device(const PrimePlan<T> *pl, T *out, const T *terms, cons
 SplitArgs native_split_args(const cntt_native *pl, void *const *res);
 int native_split_device(const cntt_native *pl, const void *value, void *const *res, size_t count, bool binary, hipStream_t st);
 int native_crt_device(const cntt_native *pl, void *value, void *const *res, size_t count, hipStream_t st);
+int native_ntt_device(const cntt_native *pl, void *const *res, size_t batch, bool inv, hipStream_t st);
+// Plan32 kinds: the nprimes monomial tables of the multi-bit bootstrap on the current device (native_multibit.hpp), built on first use
+int native_multibit_tables(const cntt_native *pl, const uint32_t **tab);
 
 // CNTT_OK: enqueued; FUSED_NONE: no fused kernel for this plan / size (the caller composes)
 constexpr int FUSED_NONE = -1;

@@ -32,7 +32,16 @@ struct Workspace {
 struct NativeCache {
     std::mutex mu;
     std::map<int, Workspace> ws;
+    // nprimes x n words psi_i^m n^-1 R^2 mod P_i, R = 2^32 (native_multibit.hpp), per device: built by the plan's first multi-bit call there
+    std::map<int, uint32_t *> mono;
     ~NativeCache() {
+        for (auto &kv : mono) {
+            int cur = 0;
+            if (hipGetDevice(&cur) != hipSuccess) continue;
+            (void)hipSetDevice(kv.first);
+            (void)hipFree(kv.second);
+            (void)hipSetDevice(cur);
+        }
         for (auto &kv : ws) {
             int cur = 0;
             if (hipGetDevice(&cur) != hipSuccess) continue;
@@ -361,7 +370,43 @@ int native_crt_device(const cntt_native *pl, void *value, void *const *res, size
     HIP_TRY(hipGetLastError());
     return CNTT_OK;
 }
-static int native_ntt_device(const cntt_native *pl, void *const *res, size_t batch, bool inv, hipStream_t st) {
+// The monomial tables of the multi-bit bootstrap (include/cntt_multibit.h, native_multibit.hpp): tab[i][m] = psi_i^m n^-1 R^2 mod P_i for
+// m < n, psi_i the root of sub-plan i and R = 2^32, nprimes x n words in one allocation per (plan, device).  Built on the host by the
+// first multi-bit call of the plan on the device, under the cache's mutex: a synchronous allocation and copy, so that call may not sit
+// inside a stream capture ("First call" in the header).  Later calls: one lock, one look-up.
+int native_multibit_tables(const cntt_native *pl, const uint32_t **tab) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const size_t n = pl->n;
+    const int k = pl->info.nprimes;
+    std::lock_guard<std::mutex> lk(pl->cache->mu);
+    uint32_t *&d = pl->cache->mono[dev];
+    if (!d) {
+        std::vector<uint32_t> host((size_t)k * n);
+        for (int i = 0; i < k; ++i) {
+            const cntt_plan32 *sub = pl->p32[(size_t)i].get();
+            const uint64_t p = sub->p;
+            uint64_t x = host::mulmod((uint64_t)sub->mp.r2, (uint64_t)sub->n_inv, p);
+            for (size_t m = 0; m < n; ++m) {
+                host[(size_t)i * n + m] = (uint32_t)x;
+                x = host::mulmod(x, sub->root, p);
+            }
+        }
+        uint32_t *fresh = nullptr;
+        if (hipMalloc((void **)&fresh, host.size() * sizeof(uint32_t)) != hipSuccess)
+            return fail(CNTT_ENOMEM, "hipMalloc of the monomial tables failed");
+        const hipError_t c = hipMemcpy(fresh, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (c != hipSuccess) {
+            (void)hipFree(fresh);
+            return fail(CNTT_EDEVICE, "upload of the monomial tables failed: %s", hipGetErrorString(c));
+        }
+        d = fresh;
+    }
+    for (int i = 0; i < k; ++i) tab[i] = d + (size_t)i * n;
+    return CNTT_OK;
+}
+// the transforms of the sub-plans on `res`; public to the other host units (host_common.hpp)
+int native_ntt_device(const cntt_native *pl, void *const *res, size_t batch, bool inv, hipStream_t st) {
     for (int i = 0; i < pl->info.nprimes; ++i) {
         int rc = pl->info.is52 ? ntt_device<uint64_t>(pl->p64[(size_t)i].get(), (uint64_t *)res[i], batch, inv, st)
                                : ntt_device<uint32_t>(pl->p32[(size_t)i].get(), (uint32_t *)res[i], batch, inv, st);

@@ -433,3 +433,8 @@ extern "C" int cntt_native_pack_keyswitch_batch(const cntt_native_t *pl, void *g
     return pack_keyswitch<NativePbs>(pl, glwe_out, lwe_in, pksk_ntt, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, workspace,
                                       workspace_bytes, where, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// multi-bit blind rotation and bootstrap (include/cntt_multibit.h, native_multibit.hpp)
+// ---------------------------------------------------------------------------------------------
+#include "host_native_multibit.inc"

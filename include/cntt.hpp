@@ -22,6 +22,7 @@
 
 #include "cntt.h"
 #include "cntt_ext.h"
+#include "cntt_multibit.h"
 #include "cntt_prime_keyswitch.h"
 #include "cntt_prime_multibit.h"
 #include "cntt_prime_pack.h"
@@ -408,6 +409,30 @@ template <cntt_native_kind_t KIND, class R, int NPRIMES, int WORD_BYTES> class N
                               size_t workspace_bytes = 0, cntt_mem_t where = CNTT_MEM_DEVICE, void *stream = nullptr) const {
         check(cntt_native_pack_keyswitch_batch(h_, glwe_out, lwe_in, pksk_ntt, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch,
                                                workspace, workspace_bytes, where, stream));
+    }
+    // multi-bit blind rotation and bootstrap (cntt_multibit.h; Plan32 kinds): groups of `grouping` mask words, one bundled external
+    // product each; bsk_mb = the residue planes cntt_native_fwd_batch writes for (lwe_dim / grouping) * 2^grouping GGSW ciphertexts
+    size_t multibit_pbs_workspace_bytes(size_t lwe_dim, size_t glwe_dim, unsigned levels, unsigned grouping, size_t batch) const {
+        return cntt_native_multibit_pbs_workspace_bytes(h_, lwe_dim, glwe_dim, levels, grouping, batch);
+    }
+    void multibit_accumulate_batch(void *const *out_ntt, const void *const *terms_ntt, const uint32_t *rot_rows, const void *const *key_group,
+                                   size_t nterms, size_t nout, unsigned grouping, size_t batch, cntt_mem_t where = CNTT_MEM_DEVICE,
+                                   void *stream = nullptr) const {
+        check(cntt_native_multibit_accumulate_batch(h_, out_ntt, terms_ntt, rot_rows, key_group, nterms, nout, grouping, batch, where, stream));
+    }
+    void multibit_blind_rotate_batch(void *acc, const void *lut, bool lut_per_element, const uint32_t *rot_t, const void *const *bsk_mb,
+                                     size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels, unsigned grouping, size_t batch,
+                                     void *workspace = nullptr, size_t workspace_bytes = 0, cntt_mem_t where = CNTT_MEM_DEVICE,
+                                     void *stream = nullptr) const {
+        check(cntt_native_multibit_blind_rotate_batch(h_, acc, lut, lut_per_element ? 1 : 0, rot_t, bsk_mb, lwe_dim, glwe_dim, base_log,
+                                                      levels, grouping, batch, workspace, workspace_bytes, where, stream));
+    }
+    void multibit_bootstrap_batch(void *lwe_out, const void *lwe_in, const void *lut, bool lut_per_element, const void *const *bsk_mb,
+                                  size_t lwe_dim, size_t glwe_dim, unsigned base_log, unsigned levels, unsigned grouping, size_t batch,
+                                  void *workspace = nullptr, size_t workspace_bytes = 0, cntt_mem_t where = CNTT_MEM_DEVICE,
+                                  void *stream = nullptr) const {
+        check(cntt_native_multibit_bootstrap_batch(h_, lwe_out, lwe_in, lut, lut_per_element ? 1 : 0, bsk_mb, lwe_dim, glwe_dim, base_log,
+                                                   levels, grouping, batch, workspace, workspace_bytes, where, stream));
     }
 };
 }  // namespace detail
