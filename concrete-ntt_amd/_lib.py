@@ -102,6 +102,15 @@ def lib():
             "multibit_bootstrap_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint,
                                                  ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
             "multibit_pbs_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz]),
+            # include/cntt_prime_automorphism.h
+            "automorphism_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, c_int, c_vp]),
+            "automorphism_ntt_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, c_int, c_vp]),
+            "glwe_automorphism_keyswitch_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_int, c_sz, c_vp,
+                                                          c_sz, c_int, c_vp]),
+            "glwe_automorphism_keyswitch_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
+            "glwe_trace_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int,
+                                         c_vp]),
+            "glwe_trace_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, p + name)
@@ -150,6 +159,7 @@ def lib():
                                                      c_int, c_vp]),
         "cntt_native_pack_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
         "cntt_prime_multibit_grid": (ctypes.c_uint, [c_sz]),
+        "cntt_prime_automorphism_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
         # include/cntt_multibit.h
         "cntt_native_multibit_grid": (ctypes.c_uint, [c_sz]),
         "cntt_native_multibit_accumulate_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, c_sz, c_int, c_vp]),

@@ -284,6 +284,68 @@ class PrimePlan(PbsMixin):
         check(self._fn("pack_keyswitch_batch")(self._h, op, ip, kp, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, wp, wb, where,
                                                stream))
 
+    # -- ring automorphism, Galois keyswitch and trace mod p (include/cntt_prime_automorphism.h) -------------------------------------------
+    def _automorphism(self, name, out, inp, t):
+        op, ob, where, stream = self._batch(out)
+        ip, ib, iw, _ = self._batch(inp)
+        if ob != ib or iw != where:
+            raise Panic("out and in must hold the same number of polynomials in the same memory")
+        check(self._fn(name)(self._h, op, ip, t, 1, ob, where, stream))
+
+    def automorphism_batch(self, out, inp, t):
+        """out = sigma_t(inp), f(X) -> f(X^t) in Z_p[X]/(X^n + 1), on every polynomial of inp; t odd, 1 <= t < 2n.  out is only written
+        and may not overlap inp."""
+        self._automorphism("automorphism_batch", out, inp, t)
+
+    def automorphism_ntt_batch(self, out_ntt, in_ntt, t):
+        """The same map on NTT-domain polynomials, a pure permutation: automorphism_ntt_batch(fwd f) = fwd(sigma_t f)."""
+        self._automorphism("automorphism_ntt_batch", out_ntt, in_ntt, t)
+
+    def glwe_automorphism_keyswitch_workspace_bytes(self, glwe_dim, levels, batch):
+        """Bytes of workspace glwe_automorphism_keyswitch_batch needs: the negated digit polynomials, rounded up to 256 bytes."""
+        if min(glwe_dim, batch) < 0 or levels <= 0:
+            raise Panic("glwe_dim and batch must not be negative, levels >= 1")
+        return self._fn("glwe_automorphism_keyswitch_workspace_bytes")(self._h, glwe_dim, levels, batch)
+
+    def glwe_trace_workspace_bytes(self, glwe_dim, levels, batch):
+        """Bytes of workspace glwe_trace_batch needs: the digits of one step and the second ciphertext the steps alternate with."""
+        if min(glwe_dim, batch) < 0 or levels <= 0:
+            raise Panic("glwe_dim and batch must not be negative, levels >= 1")
+        return self._fn("glwe_trace_workspace_bytes")(self._h, glwe_dim, levels, batch)
+
+    def _glwe_pair(self, glwe_out, glwe_in, ak_ntt, keys, glwe_dim, base_log, levels):
+        op, oc, where, stream = self._words(glwe_out)
+        ip, ic, iw, _ = self._words(glwe_in)
+        per = (glwe_dim + 1) * self._n
+        if glwe_dim < 0 or levels <= 0 or base_log <= 0 or keys < 0 or ic % per or oc != ic or iw != where:
+            raise Panic("glwe_in and glwe_out: batch*(glwe_dim+1) polynomials each in the same memory; base_log, levels >= 1")
+        kp = None
+        if keys * glwe_dim:
+            kp, kc, kw, _ = self._words(ak_ntt)
+            if kw != where or kc != keys * glwe_dim * levels * per:
+                raise Panic("ak_ntt: glwe_dim*levels*(glwe_dim+1) NTT-domain polynomials per key in the memory of the other buffers")
+        return op, ip, kp, ic // per, where, stream
+
+    def glwe_automorphism_keyswitch_batch(self, glwe_out, glwe_in, ak_ntt, t, glwe_dim, base_log, levels, add_input=False, workspace=None):
+        """glwe_out[b] = AutoKS_t(glwe_in[b]) (+ glwe_in[b] with add_input): body sigma_t(body), minus the external product of the digits
+        of the permuted mask polynomials with ak_ntt, whose row (r, l) is a GLWE encryption under S of sigma_t(S_r) * 2^(W - base_log*l),
+        stored as n^-1 * fwd (fwd_batch, then normalize_batch).  The phase of the output is sigma_t of the phase of the input.
+        workspace: None (one allocation per call) or a buffer of glwe_automorphism_keyswitch_workspace_bytes()."""
+        op, ip, kp, batch, where, stream = self._glwe_pair(glwe_out, glwe_in, ak_ntt, 1, glwe_dim, base_log, levels)
+        wp, wb = self._workspace(workspace, where)
+        check(self._fn("glwe_automorphism_keyswitch_batch")(self._h, op, ip, kp, t, glwe_dim, base_log, levels, 1 if add_input else 0, batch,
+                                                            wp, wb, where, stream))
+
+    def glwe_trace_batch(self, glwe_out, glwe_in, ak_ntt, steps, glwe_dim, base_log, levels, workspace=None):
+        """`steps` rounds of cur <- cur + AutoKS_(n/2^r + 1)(cur), r = 0 .. steps-1: coefficient i of the phase becomes 2^steps * phase[i]
+        where 2^steps divides i and 0 elsewhere (scale by the inverse of 2^steps mod p afterwards).  ak_ntt: the `steps` keys back to
+        back; workspace: None or a buffer of glwe_trace_workspace_bytes()."""
+        if steps < 0:
+            raise Panic("steps must not be negative")
+        op, ip, kp, batch, where, stream = self._glwe_pair(glwe_out, glwe_in, ak_ntt, steps, glwe_dim, base_log, levels)
+        wp, wb = self._workspace(workspace, where)
+        check(self._fn("glwe_trace_batch")(self._h, op, ip, kp, steps, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
+
     # -- multi-bit blind rotation and bootstrap mod p (include/cntt_prime_multibit.h) ------------------------------------------------------
     def multibit_pbs_workspace_bytes(self, lwe_dim, glwe_dim, levels, grouping, batch):
         """Bytes of workspace multibit_bootstrap_batch needs (digits + rot_t + accumulator, each 256-byte aligned); enough for

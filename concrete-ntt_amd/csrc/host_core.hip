@@ -44,8 +44,8 @@ namespace {
 struct SwitchDef { const char *name; int dflt; };
 constexpr SwitchDef kSwitches[DBG_COUNT] = {
     {"fp", 1}, {"pm64", 1}, {"blk", 1}, {"mul32_blk", 1}, {"ext32_blk", 1}, {"ext_one", 1}, {"ext_split", -1}, {"native_acc", 1},
-    {"product_fused", -1}, {"plan52_via32", 1}, {"native_ext", 1}, {"native_gadget", 0}, {"walk_split", 1}};
-std::atomic<int> g_switch[DBG_COUNT] = {{1}, {1}, {1}, {1}, {1}, {1}, {-1}, {1}, {-1}, {1}, {1}, {0}, {1}};
+    {"product_fused", -1}, {"plan52_via32", 1}, {"native_ext", 1}, {"native_gadget", 0}, {"walk_split", 1}, {"autom_lds", 1}};
+std::atomic<int> g_switch[DBG_COUNT] = {{1}, {1}, {1}, {1}, {1}, {1}, {-1}, {1}, {-1}, {1}, {1}, {0}, {1}, {1}};
 int switch_index(const char *key) {
     if (!key) return -1;
     for (int i = 0; i < (int)DBG_COUNT; ++i)

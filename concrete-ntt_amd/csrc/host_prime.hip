@@ -576,3 +576,5 @@ template int external_product_device<uint64_t>(const PrimePlan<uint64_t> *, uint
 #include "host_prime_pack.inc"
 // the multi-bit bootstrap mod p (include/cntt_prime_multibit.h)
 #include "host_prime_multibit.inc"
+// the ring automorphism, the Galois keyswitch and the trace mod p (include/cntt_prime_automorphism.h)
+#include "host_prime_automorphism.inc"

@@ -24,6 +24,7 @@ enum DebugSwitch : int {
     DBG_NATIVE_EXT,     // 1 (default): fused external-product kernel of the native Plan32 kinds (native_ext.hpp); 0: composed pipeline
     DBG_NATIVE_GADGET,  // 0 (default): external product on undecomposed polynomials = decompose, then the external product; 1: the fused kernel (native_gadget.hpp), measured slower
     DBG_WALK_SPLIT,     // 1 (default): the persistent walks of wave-private polynomials (ntt_kernel_wp / mul_kernel_wp, TPP <= 64) hand the leftovers of the last round out one wavefront at a time over all CUs; 0: tile by tile
+    DBG_AUTOM_LDS,      // 1 (default): the automorphism kernels (prime_automorphism.hpp) stage polynomials of up to 64 KiB through LDS; 0: gather from global memory
     DBG_COUNT
 };
 int debug_switch(DebugSwitch key);

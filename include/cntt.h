@@ -118,6 +118,8 @@ int cntt_shard_bounds(size_t batch, int world, int rank, size_t *begin, size_t *
 /*   "walk_split"        1     persistent walks of polynomials that live in one wavefront (ntt_kernel_wp / mul_kernel_wp, n <= 1024    */
 /*                             for 64-bit words): the leftovers of the last round go out one wavefront at a time over all CUs;        */
 /*                             0: tile by tile to the first workgroups                                                                */
+/*   "autom_lds"         1     kernels of cntt_prime_automorphism.h: polynomials of up to 64 KiB staged through LDS before the gather; */
+/*                             0: gather from global memory (what larger polynomials always take)                                     */
 /* value -1 restores a switch's default; key "reset" restores all.  Process-wide, thread-safe (atomics); the two class switches are    */
 /* recorded in the plan at creation (cntt_prime*_plan_info().arith_class reports the class in use), the others are read per call.      */
 /* ------------------------------------------------------------------------------------- */
