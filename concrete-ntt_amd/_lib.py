@@ -111,6 +111,13 @@ def lib():
             "glwe_trace_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int,
                                          c_vp]),
             "glwe_trace_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
+            # include/cntt_prime_ring_pack.h
+            "glwe_embed_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_int, c_vp]),
+            "glwe_merge_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int,
+                                         c_vp]),
+            "glwe_merge_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
+            "ring_pack_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
+            "ring_pack_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, c_sz]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, p + name)
@@ -160,6 +167,7 @@ def lib():
         "cntt_native_pack_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
         "cntt_prime_multibit_grid": (ctypes.c_uint, [c_sz]),
         "cntt_prime_automorphism_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
+        "cntt_prime_ring_pack_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
         # include/cntt_multibit.h
         "cntt_native_multibit_grid": (ctypes.c_uint, [c_sz]),
         "cntt_native_multibit_accumulate_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, c_sz, c_int, c_vp]),

@@ -578,3 +578,5 @@ template int external_product_device<uint64_t>(const PrimePlan<uint64_t> *, uint
 #include "host_prime_multibit.inc"
 // the ring automorphism, the Galois keyswitch and the trace mod p (include/cntt_prime_automorphism.h)
 #include "host_prime_automorphism.inc"
+// ring packing of LWE ciphertexts through automorphisms mod p (include/cntt_prime_ring_pack.h)
+#include "host_prime_ring_pack.inc"
