@@ -323,6 +323,18 @@ template <class T, int CLS> struct Bfly {
             x = mont_mul(x, P.n_inv, P.p, P.pinv_neg);  // n_inv field = N^-1 R^2: x / R * (N^-1 R^2) / R ... see mul_for_inv
         }
     }
+    // inv_norm at the join of the fused N = 1024 product (MulWp, round 17), 64-bit lazy class: the sum goes into its 1/N product
+    // unreduced.  Ranges: x, y in [0, 2p) (outputs of the stage before: a reduced sum or a Shoup product), so x + y < 4p < 2^64
+    // for every p of the class (p < 2^62) -- no wrap; shoup_core takes ANY word below 2^64 (ws = floor(w 2^64 / p) makes the quotient
+    // floor(y ws / 2^64) short of y w / p by less than 2 whatever y is) and returns [0, 2p), what finish_inv expects.  inv_norm's csub_two_p in front of that
+    // product only moved the sum from [0, 4p) to [0, 2p): four instructions per butterfly for nothing.  The difference branch
+    // is inv's: d = x + 2p - y in (0, 4p), product in [0, 2p).
+    static __device__ __forceinline__ void inv_norm_join(T &x, T &y, const ModParams<T> &P) {
+        static_assert(CLS == CLS_LAZY && sizeof(T) == 8, "the 64-bit lazy class only");
+        const T d = (x + P.two_p) - y;
+        x = shoup_mul<T, true>(x + y, P.n_inv, P.n_inv_shoup, P.neg_p);
+        y = shoup_mul<T, true>(d, P.last_w, P.last_w_shoup, P.neg_p);
+    }
     static constexpr bool IS_FP = false;
     static constexpr bool FUSED_LAZY = false;  // the fused kernels hand canonical values to the pointwise product
     // a word as loaded from memory -> the class's register form (identity for the integer classes)
@@ -743,6 +755,65 @@ template <class T, int CLS> __device__ __forceinline__ T mul_fused(T a, T b, con
     } else {
         return mul_for_inv<T, CLS>(a, b, P);
     }
+}
+// ---------------------------------------------------------------------------------------------
+// The same Montgomery product at the join of the fused N = 1024 product (MulWp, round 17; 64-bit lazy class), with the positive inverse
+// k = p^-1 mod 2^64 instead of -p^-1:   m = lo(a b) k,   u = hi(a b) + p - hi(m p).
+// m p = a b (mod 2^64), so the low words cancel EXACTLY and (a b - m p) / 2^64 = hi(a b) - hi(m p): no "lo != 0" carry to rebuild.
+// Ranges: a < 4p < 2^64 (the forward transform's lazy output), b <= p - 1 (a canonical word of rhs_ntt) => hi(a b) <= p - 1;
+// m < 2^64 => hi(m p) <= p - 1; so u lies in [1, 2p - 1], inside the [0, 2p) the inverse butterflies take, and hi(a b) + p < 2p < 2^63
+// does not wrap.  u = a b 2^-64 (mod p) as in mul_fused (it is mul_fused's word, or that word + p where lo(a b) = 0).
+// From the plain C++ of mul_fused hipcc builds each 64 x 64 product with zero-extension moves and a three-add carry chain (27
+// instructions per coefficient, profiles/r17_fused_join_census.txt); here the two high words take shoup_core's route -- the carry of
+// the cross-product sum comes out of v_mad_u64_u32 itself -- and the low word of a b is read off that same sum: 21 per coefficient,
+// the same twelve multiplies.  Scratch pair v[2:3] as in shoup_core; the v_cndmask sits three (two) instructions behind the
+// v_mad that writes its carry register (gfx950: two wait states between a VALU write of an SGPR and a VALU read of it).
+// ---------------------------------------------------------------------------------------------
+// a b = hi 2^64 + lo
+__device__ __forceinline__ void mul_wide_join(uint64_t a, uint64_t b, uint64_t &lo, uint64_t &hi) {
+    const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
+    const uint64_t t = __umulhi(a0, b0);
+    const uint64_t u = (uint64_t)a1 * b0 + t;  // cannot overflow
+    uint32_t l0, l1;
+    uint64_t carry;
+    // a0 b1 + u: its low word is bits 32..63 of a b, its upper word and carry are bits 64..96 of the cross sum
+    asm("v_mad_u64_u32 v[2:3], %[c], %[a0], %[b1], %[u]\n\t"
+        "v_mul_lo_u32 %[l0], %[a0], %[b0]\n\t"
+        "v_mov_b32 %[l1], v2\n\t"
+        "v_mov_b32 v2, v3\n\t"
+        "v_cndmask_b32_e64 v3, 0, 1, %[c]\n\t"
+        "v_mad_u64_u32 %[h], vcc, %[a1], %[b1], v[2:3]"
+        : [h] "=&v"(hi), [l0] "=&v"(l0), [l1] "=&v"(l1), [c] "=&s"(carry)
+        : [a0] "v"(a0), [a1] "v"(a1), [b0] "v"(b0), [b1] "v"(b1), [u] "v"(u)
+        : "vcc", "v2", "v3");
+    lo = ((uint64_t)l1 << 32) | l0;
+}
+// (x + p) - hi(m p), p wave-uniform
+__device__ __forceinline__ uint64_t mont_fold_join(uint64_t m, uint64_t p, uint64_t x) {
+    const uint32_t m0 = (uint32_t)m, m1 = (uint32_t)(m >> 32), p0 = (uint32_t)p, p1 = (uint32_t)(p >> 32);
+    const uint64_t t = __umulhi(m0, p0);
+    const uint64_t u = (uint64_t)m1 * p0 + t;  // cannot overflow
+    uint64_t q, xp, carry;
+    asm("v_mad_u64_u32 v[2:3], %[c], %[m0], %[p1], %[u]\n\t"
+        "v_lshl_add_u64 %[xp], %[x], 0, %[p]\n\t"
+        "v_mov_b32 v2, v3\n\t"
+        "v_cndmask_b32_e64 v3, 0, 1, %[c]\n\t"
+        "v_mad_u64_u32 %[q], vcc, %[m1], %[p1], v[2:3]"
+        : [q] "=&v"(q), [xp] "=&v"(xp), [c] "=&s"(carry)
+        : [m0] "v"(m0), [m1] "v"(m1), [p1] "s"(p1), [p] "s"(p), [x] "v"(x), [u] "v"(u)
+        : "vcc", "v2", "v3");
+    return xp - q;
+}
+// p^-1 mod 2^64 in scalar registers (opaque: from lo * (0 - pinv_neg) hipcc negates lo in every lane instead)
+__device__ __forceinline__ uint64_t mul_join_pinv(const ModParams<uint64_t> &P) {
+    uint64_t k = (uint64_t)0 - P.pinv_neg;
+    asm("" : "+s"(k));
+    return k;
+}
+__device__ __forceinline__ uint64_t mul_fused_join(uint64_t a, uint64_t b, const ModParams<uint64_t> &P, uint64_t pinv) {
+    uint64_t lo, hi;
+    mul_wide_join(a, b, lo, hi);
+    return mont_fold_join(lo * pinv, P.p, hi);
 }
 // an accumulator of the fused chains -> what the inverse transform's first stage accepts (Montgomery classes: times 2^B, in [0, 2p))
 template <class T, int CLS> __device__ __forceinline__ T chain_pre_inverse(T v, const ModParams<T> &P) {

@@ -75,6 +75,9 @@ template <> struct VecOf<uint32_t, 1> { using type = uint32_t; };
 template <> struct VecOf<uint32_t, 2> { using type = __attribute__((ext_vector_type(2))) uint32_t; };
 template <> struct VecOf<uint32_t, 4> { using type = __attribute__((ext_vector_type(4))) uint32_t; };
 
+// NORM of NttKernel::stage: which form of the last inverse stage
+enum : int { NORM_NONE = 0, NORM_INV = 1, NORM_JOIN = 2 };
+
 // ---- the kernel -----------------------------------------------------------------------------
 template <class T, int LOGN, bool INV, int CLS, bool SUB, int FAM = 0>
 struct NttKernel {
@@ -416,10 +419,11 @@ struct NttKernel {
     }
 
     // NORM (inverse only): the stage on the top index bit -- the last one, one twiddle inv_twid[1] for all of its
-    // butterflies -- also applies the 1/N normalisation (Bfly::inv_norm).
+    // butterflies -- also applies the 1/N normalisation (Bfly::inv_norm; NORM_JOIN: Bfly::inv_norm_join, the fused
+    // N = 1024 product of the 64-bit lazy class).
     // R: the register form of a coefficient -- T itself, or (32-bit lazy class) a 64-bit "box" whose low word is the
     // value and whose high word is don't-care, the form in which x + y w + q (-p) is two v_mad_u64_u32 (BoxOps).
-    template <int K, int GI, bool IMG = false, bool NORM = false, int TWC = 0, class R = T>
+    template <int K, int GI, bool IMG = false, int NORM = 0, int TWC = 0, class R = T>
     static __device__ __forceinline__ void stage(R (&r)[E], uint32_t ebase, uint32_t qpre, uint32_t depth,
                                                  const TwPair<T> *__restrict__ tw, const ModParams<T> &P,
                                                  uint32_t tid = 0, const TwPair<T> *img = nullptr) {
@@ -436,7 +440,8 @@ struct NttKernel {
 #pragma unroll
             for (int j = 0; j < E; ++j) {
                 if ((j >> k) & 1) continue;
-                if constexpr (std::is_same<R, T>::value) Bfly<T, CLS>::inv_norm(r[j], r[j | (1 << k)], P);
+                if constexpr (NORM == NORM_JOIN) Bfly<T, CLS>::inv_norm_join(r[j], r[j | (1 << k)], P);
+                else if constexpr (std::is_same<R, T>::value) Bfly<T, CLS>::inv_norm(r[j], r[j | (1 << k)], P);
                 else BoxOps<CLS>::inv_norm(r[j], r[j | (1 << k)], P);
             }
             return;
@@ -521,7 +526,7 @@ struct NttKernel {
         }
     }
 
-    template <int K, int GI, bool IMG, bool NORM, int TWC, class R>
+    template <int K, int GI, bool IMG, int NORM, int TWC, class R>
     static __device__ __forceinline__ void stages_r(R (&r)[E], uint32_t ebase, uint32_t qpre, uint32_t depth,
                                                     const TwPair<T> *__restrict__ tw, const ModParams<T> &P, uint32_t tid,
                                                     const TwPair<T> *img) {
@@ -531,7 +536,7 @@ struct NttKernel {
         }
     }
     // all register-resident stages of pass K
-    template <int K, int GI = 0, bool IMG = false, bool NORM = false, int TWC = 0>
+    template <int K, int GI = 0, bool IMG = false, int NORM = 0, int TWC = 0>
     static __device__ __forceinline__ void stages(T (&r)[E], uint32_t ebase, uint32_t qpre, uint32_t depth,
                                                   const TwPair<T> *__restrict__ tw, const ModParams<T> &P,
                                                   uint32_t tid = 0, const TwPair<T> *img = nullptr) {
@@ -671,7 +676,7 @@ struct NttWp : NttKernel<T, LOGN, INV, CLS, false, FAM> {
     // global memory (L2), for kernels that walk several primes and cannot hold an image per prime
     // FIN: bring the outputs into [0, p) (what memory holds); fused kernels whose next step takes the class's lazy
     // register form (CLS_FP products) skip it
-    template <int K, bool NORM = false, bool IMG = true, bool FIN = true, int TWC = 0>
+    template <int K, int NORM = 0, bool IMG = true, bool FIN = true, int TWC = 0>
     static __device__ __forceinline__ void pass(T (&r)[E], T *lds, uint32_t tid, const TwPair<T> *__restrict__ tw,
                                                 const TwPair<T> *img, const ModParams<T> &P) {
         constexpr uint32_t RM = S::RMASK[K], CM = FULL & ~RM;
@@ -813,6 +818,10 @@ struct MulWp {
     static constexpr uint32_t RM0 = FB::S::RMASK[0], RMM = FB::S::RMASK[NPASS - 1], RML = IB::S::RMASK[NPASS - 1];
     static_assert(RMM == IB::S::RMASK[0], "forward and inverse schedules must mirror each other");
     static constexpr uint32_t IO_RM = F::IO_RM;
+    // Round 17, the headline shape only (64-bit lazy class, N = 1024: the one whose join was counted section by section,
+    // profiles/r17_fused_join_census.txt, and measured): the pointwise product is mul_fused_join and the last inverse stage
+    // Bfly::inv_norm_join (ntt_arith.hpp: ranges at both sites).  Every other instance keeps mul_fused / inv_norm.
+    static constexpr bool JOIN = sizeof(T) == 8 && CLS == CLS_LAZY && LOGN == 10;
 
     static __device__ __forceinline__ void run(T *__restrict__ lhs, const T *__restrict__ rhs_ntt,
                                                const TwPair<T> *__restrict__ twf, const TwPair<T> *__restrict__ twi,
@@ -821,6 +830,8 @@ struct MulWp {
         FB::fill_image(imgf, twf);
         IB::fill_image(imgi, twi);
         __syncthreads();
+        [[maybe_unused]] uint64_t pinv = 0;   // JOIN: p^-1 mod 2^64 (scalar registers)
+        if constexpr (JOIN) pinv = mul_join_pinv(P);
         const ModParams<T> Pi = mul_inv_params<T, CLS>(P);   // the inverse half's constants (lazy class: times 2^B, see mul_fused)
         const uint32_t tid = threadIdx.x & (TPP - 1);
         const uint32_t pl = threadIdx.x / TPP;
@@ -874,10 +885,13 @@ struct MulWp {
                 FB::template gather_tile<RMM>(b, rhs_ntt + ((size_t)base << LOGN),
                                               ((plc << LOGN) + ebaseM) * (uint32_t)sizeof(T));
 #pragma unroll
-                for (int j = 0; j < E; ++j) r[j] = mul_fused<T, CLS>(r[j], b[j], P);  // 1/N: inside the last inverse stage
+                for (int j = 0; j < E; ++j) {  // 1/N: inside the last inverse stage
+                    if constexpr (JOIN) r[j] = mul_fused_join(r[j], b[j], P, pinv);
+                    else r[j] = mul_fused<T, CLS>(r[j], b[j], P);
+                }
             }
             F::wsync();  // the forward transform's last exchange has been read before the inverse overwrites it
-            I::template pass<0, true>(r, lds, tid, twi, imgi, Pi);  // canonical coefficients, layout RML
+            I::template pass<0, JOIN ? NORM_JOIN : NORM_INV>(r, lds, tid, twi, imgi, Pi);  // canonical coefficients, layout RML
             if constexpr (RML != IO_RM) {
                 F::wsync();
                 FB::template scatter<RML>(r, lds, ebaseL, true);
