@@ -75,7 +75,9 @@ inline unsigned ew_grid(size_t work_items) {
 
 // Working set (bytes one call reads and writes) above which the stand-alone transforms and the pointwise kernels take the
 // non-temporal policy.  384 MiB is 1.5 x the 256 MiB Infinity Cache: batches that fit the cache lost 3-17 % with the hint.
-// tests/test_gpu_multitrip_transforms.py (STREAM_BYTES) restates this number for the streaming tests.
+// The streaming tests restate this number (STREAM_BYTES): tests/test_gpu_multitrip_transforms.py (for test_gpu_streamed_batches.py),
+// test_gpu_native_gadget.py, test_gpu_native_pbs.py, test_gpu_prime_pbs.py and tests/streaming_cases.py (for
+// test_gpu_prime_streaming.py, with the byte count of every launch site that compares against it).
 constexpr size_t STREAM_BYTES = (size_t)384 << 20;
 
 // The host-slice path (CNTT_MEM_HOST) of every call: device copies of the caller's buffers.  in / inout enqueue their host-to-device
