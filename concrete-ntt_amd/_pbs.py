@@ -8,8 +8,10 @@ class PbsMixin:
     """What the host class supplies:
     _words(buf) -> (pointer, word count, memory, stream) of a buffer of the plan's words;
     _bsk(key, where, lwe_dim, glwe_dim, levels) -> the bootstrapping key as the C call takes it, its shape and memory checked;
+    _bsk_mb(key, where, lwe_dim, glwe_dim, levels, grouping) -> the same for the multi-bit key;
     _fn(name) -> the C entry point `name` of the plan's family;
-    blind_rotate_batch and bootstrap_batch, which name the key argument their way and pass on to _blind_rotate / _bootstrap."""
+    blind_rotate_batch and bootstrap_batch, which name the key argument their way and pass on to _blind_rotate / _bootstrap, and their
+    multibit_* forms, which pass a `grouping` as well."""
 
     SRC_MODES = {"plain": 0, "rotate": 1, "cmux": 2}
 
@@ -87,21 +89,34 @@ class PbsMixin:
             raise Panic("lwe: batch*(lwe_dim+1) words; rot_t: as many uint32 in the same memory")
         check(self._fn("lwe_modswitch_batch")(self._h, rp, lp, lwe_dim, lc // (lwe_dim + 1), where, stream))
 
-    def _blind_rotate(self, acc, lut, rot_t, bsk, lwe_dim, glwe_dim, base_log, levels, workspace, lut_per_element):
-        """blind_rotate_batch of the plan classes, which name and describe the key."""
+    def multibit_pbs_workspace_bytes(self, lwe_dim, glwe_dim, levels, grouping, batch):
+        """Bytes of workspace multibit_bootstrap_batch needs (digits + the family's scratch + rot_t + accumulator, each 256-byte aligned:
+        the plan class says what the scratch is); enough for multibit_blind_rotate_batch too."""
+        if min(lwe_dim, glwe_dim, levels, grouping, batch) < 0:
+            raise Panic("lwe_dim, glwe_dim, levels, grouping and batch must not be negative")
+        return self._fn("multibit_pbs_workspace_bytes")(self._h, lwe_dim, glwe_dim, levels, grouping, batch)
+
+    def _key_call(self, name, bsk, where, lwe_dim, glwe_dim, levels, grouping):
+        """(the key as the C call takes it, the entry point, what it takes between levels and batch): the classic call, or with a
+        `grouping` its multi-bit form."""
+        if grouping is None:
+            return self._bsk(bsk, where, lwe_dim, glwe_dim, levels), self._fn(name), ()
+        return self._bsk_mb(bsk, where, lwe_dim, glwe_dim, levels, grouping), self._fn("multibit_" + name), (grouping,)
+
+    def _blind_rotate(self, acc, lut, rot_t, bsk, lwe_dim, glwe_dim, base_log, levels, workspace, lut_per_element, grouping=None):
+        """blind_rotate_batch and multibit_blind_rotate_batch (`grouping` given) of the plan classes, which name and describe the key."""
         ap, ac, where, stream = self._words(acc)
         n = self._n
-        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or ac % ((glwe_dim + 1) * n):
+        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or (grouping or 0) < 0 or ac % ((glwe_dim + 1) * n):
             raise Panic("acc: batch*(glwe_dim+1) polynomials; base_log, levels >= 1")
         batch = ac // ((glwe_dim + 1) * n)
         rp, rc_ = self._rot(rot_t, where, "rot_t")
         if rc_ != (lwe_dim + 1) * batch:
             raise Panic("rot_t: (lwe_dim+1)*batch uint32 in the memory of acc")
         lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
-        key = self._bsk(bsk, where, lwe_dim, glwe_dim, levels)
+        key, call, g = self._key_call("blind_rotate_batch", bsk, where, lwe_dim, glwe_dim, levels, grouping)
         wp, wb = self._workspace(workspace, where)
-        check(self._fn("blind_rotate_batch")(self._h, ap, lp, per, rp, key, lwe_dim, glwe_dim, base_log, levels, batch, wp, wb, where,
-                                             stream))
+        check(call(self._h, ap, lp, per, rp, key, lwe_dim, glwe_dim, base_log, levels, *g, batch, wp, wb, where, stream))
 
     def sample_extract_batch(self, lwe_out, glwe, glwe_dim, index=0):
         """lwe_out[b] = the LWE ciphertext (glwe_dim*n mask words, body last) of coefficient `index` of glwe[b] (glwe_dim+1 polynomials),
@@ -113,17 +128,17 @@ class PbsMixin:
             raise Panic("glwe: batch*(glwe_dim+1) polynomials; lwe_out: batch*(glwe_dim*n+1) words in the same memory")
         check(self._fn("sample_extract_batch")(self._h, op, gp, glwe_dim, index, gc // ((glwe_dim + 1) * n), where, stream))
 
-    def _bootstrap(self, lwe_out, lwe_in, lut, bsk, lwe_dim, glwe_dim, base_log, levels, workspace, lut_per_element):
-        """bootstrap_batch of the plan classes, which name the key."""
+    def _bootstrap(self, lwe_out, lwe_in, lut, bsk, lwe_dim, glwe_dim, base_log, levels, workspace, lut_per_element, grouping=None):
+        """bootstrap_batch and multibit_bootstrap_batch (`grouping` given) of the plan classes, which name the key."""
         ip, ic, where, stream = self._words(lwe_in)
         op, oc, ow, _ = self._words(lwe_out)
         n = self._n
-        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or ic % (lwe_dim + 1) or ow != where:
+        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or (grouping or 0) < 0 or ic % (lwe_dim + 1) or ow != where:
             raise Panic("lwe_in: batch*(lwe_dim+1) words; lwe_out in the same memory; base_log, levels >= 1")
         batch = ic // (lwe_dim + 1)
         if oc != batch * (glwe_dim * n + 1):
             raise Panic("lwe_out must hold batch*(glwe_dim*n+1) = %d words" % (batch * (glwe_dim * n + 1)))
         lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
-        key = self._bsk(bsk, where, lwe_dim, glwe_dim, levels)
+        key, call, g = self._key_call("bootstrap_batch", bsk, where, lwe_dim, glwe_dim, levels, grouping)
         wp, wb = self._workspace(workspace, where)
-        check(self._fn("bootstrap_batch")(self._h, op, ip, lp, per, key, lwe_dim, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
+        check(call(self._h, op, ip, lp, per, key, lwe_dim, glwe_dim, base_log, levels, *g, batch, wp, wb, where, stream))

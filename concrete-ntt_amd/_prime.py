@@ -407,13 +407,7 @@ class PrimePlan(PbsMixin):
         check(self._fn("ring_pack_batch")(self._h, op, ip, kp, lwe_count, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
 
     # -- multi-bit blind rotation and bootstrap mod p (include/cntt_prime_multibit.h) ------------------------------------------------------
-    def multibit_pbs_workspace_bytes(self, lwe_dim, glwe_dim, levels, grouping, batch):
-        """Bytes of workspace multibit_bootstrap_batch needs (digits + rot_t + accumulator, each 256-byte aligned); enough for
-        multibit_blind_rotate_batch too."""
-        if min(lwe_dim, glwe_dim, levels, grouping, batch) < 0:
-            raise Panic("lwe_dim, glwe_dim, levels, grouping and batch must not be negative")
-        return self._fn("multibit_pbs_workspace_bytes")(self._h, lwe_dim, glwe_dim, levels, grouping, batch)
-
+    #    multibit_pbs_workspace_bytes is PbsMixin's: no scratch here, so it equals pbs_workspace_bytes
     def multibit_accumulate_batch(self, out_ntt, terms_ntt, rot_rows, key_group, nterms, nout, grouping):
         """out_ntt[b][o][c] = sum_{t < 2^grouping} fwd(X^e_t(b))[c] * sum_j terms_ntt[b][j][c] * key_group[t][j][o][c] mod p, exact for
         every prime; e_t(b) = the sum of rot_rows[i*batch + b] over the set bits i of t, mod 2n.  out_ntt: batch*nout polynomials
@@ -446,34 +440,10 @@ class PrimePlan(PbsMixin):
         bsk_mb: ONE buffer of (lwe_dim/grouping)*2^grouping*(glwe_dim+1)*levels*(glwe_dim+1) polynomials holding n^-1 * fwd(key), key
         (r, t) the GGSW of prod_{i in t} s_{r*grouping+i} * prod_{i not in t} (1 - s_{r*grouping+i}).  The rest as blind_rotate_batch;
         workspace: None or a buffer of multibit_pbs_workspace_bytes()."""
-        ap, ac, where, stream = self._words(acc)
-        n = self._n
-        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or grouping < 0 or ac % ((glwe_dim + 1) * n):
-            raise Panic("acc: batch*(glwe_dim+1) polynomials; base_log, levels >= 1")
-        batch = ac // ((glwe_dim + 1) * n)
-        rp, rc_ = self._rot(rot_t, where, "rot_t")
-        if rc_ != (lwe_dim + 1) * batch:
-            raise Panic("rot_t: (lwe_dim+1)*batch uint32 in the memory of acc")
-        lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
-        key = self._bsk_mb(bsk_mb, where, lwe_dim, glwe_dim, levels, grouping)
-        wp, wb = self._workspace(workspace, where)
-        check(self._fn("multibit_blind_rotate_batch")(self._h, ap, lp, per, rp, key, lwe_dim, glwe_dim, base_log, levels, grouping, batch,
-                                                      wp, wb, where, stream))
+        self._blind_rotate(acc, lut, rot_t, bsk_mb, lwe_dim, glwe_dim, base_log, levels, workspace, lut_per_element, grouping)
 
     def multibit_bootstrap_batch(self, lwe_out, lwe_in, lut, bsk_mb, lwe_dim, glwe_dim, base_log, levels, grouping, workspace=None,
                                  lut_per_element=None):
         """lwe_modswitch_batch -> multibit_blind_rotate_batch -> sample_extract_batch(index=0) mod p in one call: lwe_in batch*(lwe_dim+1)
         words, lwe_out batch*(glwe_dim*n+1) words; rot_t and the accumulator live in the workspace (None: one allocation per call)."""
-        ip, ic, where, stream = self._words(lwe_in)
-        op, oc, ow, _ = self._words(lwe_out)
-        n = self._n
-        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or grouping < 0 or ic % (lwe_dim + 1) or ow != where:
-            raise Panic("lwe_in: batch*(lwe_dim+1) words; lwe_out in the same memory; base_log, levels >= 1")
-        batch = ic // (lwe_dim + 1)
-        if oc != batch * (glwe_dim * n + 1):
-            raise Panic("lwe_out must hold batch*(glwe_dim*n+1) = %d words" % (batch * (glwe_dim * n + 1)))
-        lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
-        key = self._bsk_mb(bsk_mb, where, lwe_dim, glwe_dim, levels, grouping)
-        wp, wb = self._workspace(workspace, where)
-        check(self._fn("multibit_bootstrap_batch")(self._h, op, ip, lp, per, key, lwe_dim, glwe_dim, base_log, levels, grouping, batch, wp, wb,
-                                                   where, stream))
+        self._bootstrap(lwe_out, lwe_in, lut, bsk_mb, lwe_dim, glwe_dim, base_log, levels, workspace, lut_per_element, grouping)

@@ -3,8 +3,9 @@
 // installed.  Every __global__ template is launched -- and so instantiated -- by exactly ONE unit; the others call the host function
 // that owns the launch, declared here and explicitly instantiated there.  Nothing declared here is exported.
 // pbs_host.hpp, on top of this file, is the host side of the programmable bootstrap as templates over the plan family, and lwe_host.hpp, on
-// top of that, the host side of the keyswitch, keyswitch + bootstrap and packing keyswitch: host_native_ext.hip and host_prime.hip (through
-// its host_prime_*.inc) each include them and instantiate them for their plans.
+// top of that, the host side of the keyswitch, keyswitch + bootstrap and packing keyswitch; multibit_host.hpp, also on top of pbs_host.hpp,
+// the host side of the multi-bit blind rotation and bootstrap: host_native_ext.hip and host_prime.hip (through its host_prime_*.inc) each
+// include them and instantiate them for their plans.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,7 +39,8 @@ int fail(int code, const char *fmt, ...);
 
 // The aliasing and alignment contract of the _batch calls (include/cntt.h, "Operands"): every operand aligned to its word, and an
 // operand the call writes disjoint from every other one; read-only operands may coincide.  Pointer comparisons only, before any device
-// call.  The later headers' calls (pbs_host.hpp, lwe_host.hpp) name their pairs one by one with ranges_overlap.
+// call.  The later headers' calls (pbs_host.hpp, lwe_host.hpp) name their pairs one by one with ranges_overlap; those of multibit_host.hpp use
+// check_operands.
 inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return abytes && bbytes && x < y + bbytes && y < x + abytes;

@@ -1,12 +1,14 @@
 // libcntt_hip.so host side, what is built on the native plans without a counterpart in the reference: the external product
 // (include/cntt_ext.h), rotation / gadget decomposition and the external product on undecomposed polynomials (include/cntt_gadget.h),
 // the programmable bootstrap (include/cntt_pbs.h), the LWE keyswitch and keyswitch + bootstrap (include/cntt_keyswitch.h), the
-// LWE-to-GLWE packing keyswitch (include/cntt_pack.h).  The last three are the templates of pbs_host.hpp and lwe_host.hpp, shared with the
-// prime plans: here are the family struct that fits them to the native plans (NativePbs) and the C ABI over them.
+// LWE-to-GLWE packing keyswitch (include/cntt_pack.h), the multi-bit blind rotation and bootstrap (include/cntt_multibit.h).  The last
+// four are the templates of pbs_host.hpp, lwe_host.hpp and multibit_host.hpp, shared with the prime plans: here are the family struct that
+// fits them to the native plans (NativePbs) and the C ABI over them (the multi-bit part: host_native_multibit.inc).
 #include <cstdio>
 
 #include "host_common.hpp"
 #include "lwe_host.hpp"
+#include "multibit_host.hpp"
 #include "native_gadget.hpp"
 #include "native_keyswitch.hpp"
 #include "native_pack.hpp"
@@ -191,9 +193,10 @@ static int native_gadget_device(const cntt_native *pl, void *terms, const void *
     });
 }
 
-// What the shared host pipelines (pbs_host.hpp, lwe_host.hpp) need to know of the native plans: words of 4, 8 or 16 bytes behind void
-// pointers, digits of the whole word, and a key of one residue plane per prime.  One struct for the bootstrap, the keyswitch and the
-// packing keyswitch (the name is from its first user), so that the combined call runs the bootstrap's own instantiation of the loop.
+// What the shared host pipelines (pbs_host.hpp, lwe_host.hpp, multibit_host.hpp) need to know of the native plans: words of 4, 8 or 16
+// bytes behind void pointers, digits of the whole word, and a key of one residue plane per prime.  One struct for the bootstrap, the
+// keyswitch, the packing keyswitch and the multi-bit bootstrap (the name is from its first user), so that the combined call runs the
+// bootstrap's own instantiation of the loop.
 #pragma GCC visibility push(hidden)
 struct NativePbs {
     using Plan = cntt_native;
@@ -275,6 +278,17 @@ struct NativePbs {
         return launch_native_pack_decompose(pl->info.word, terms, in, (uint64_t)off, (uint64_t)(off >> 64), base_log, levels, native_logn(pl),
                                             lin, m, i0, nw, batch, st);
     }
+
+    // the multi-bit blind rotation and bootstrap (multibit_host.hpp): the Plan32 kinds only; all but the first: host_native_multibit.inc
+    static bool multibit_supported(const cntt_native *pl) { return !pl->info.is52; }
+    static int multibit_plan_check(const cntt_native *pl);
+    static bool multibit_sizes_fit(const cntt_native *pl, size_t lwe_dim, size_t glwe_dim, unsigned levels, size_t batch);
+    static int multibit_check_terms(const cntt_native *pl, size_t glwe_dim, unsigned levels, unsigned grouping);
+    static constexpr int MAX_LDS_LOGN = MaxLdsLogN<uint32_t>::value;   // the sub-plans' transforms
+    static void multibit_scratch(const cntt_native *pl, size_t polys, unsigned levels, size_t *bytes);   // term planes, output planes
+    static int multibit_key_operands(const cntt_native *pl, Operand *ops, int cnt, Key bsk, size_t kb);
+    static int multibit_step(const cntt_native *pl, void *acc, void *digits, char *scratch, const MultibitSizes &Z,
+                             const uint32_t *rot_rows, Key key, size_t nterms, size_t npolys, unsigned grouping, size_t batch, hipStream_t st);
 };
 #pragma GCC visibility pop
 

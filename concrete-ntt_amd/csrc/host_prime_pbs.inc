@@ -1,9 +1,9 @@
 // Part of host_prime.hip (included at its end; kept apart so that file stays readable): the prime plans' side of the programmable
 // bootstrap (include/cntt_prime_pbs.h) -- the constants and the launch of prime_gadget_kernel (prime_pbs.hpp; launched by prime_pbs.hip),
-// what the shared pipeline (pbs_host.hpp) needs to know of these plans, and the C ABI over that pipeline.  The loop's external product is
-// external_product_device above, which it calls and does not change.
+// what the shared pipelines (pbs_host.hpp, multibit_host.hpp) need to know of these plans, and the C ABI over the first.  The loop's
+// external product is external_product_device above, which it calls and does not change.
 #include "../../include/cntt_prime_pbs.h"
-#include "pbs_host.hpp"
+#include "multibit_host.hpp"
 #include "prime_pbs.hpp"
 
 #pragma GCC visibility push(hidden)
@@ -53,7 +53,7 @@ static int gadget_device(const PrimePlan<T> *pl, T *terms, const T *polys, const
     return CNTT_OK;
 }
 
-// What the shared bootstrap pipeline needs to know of the prime plans: words of type T, digits of the bit length of p, and a key in one
+// What the shared bootstrap pipelines need to know of the prime plans: words of type T, digits of the bit length of p, and a key in one
 // buffer of T.
 template <class T> struct PrimePbs {
     using Plan = PrimePlan<T>;
@@ -87,6 +87,21 @@ template <class T> struct PrimePbs {
     }
     static constexpr auto gadget = gadget_device<T>;   // the two steps of the loop
     static constexpr auto ext_product = external_product_device<T>;
+
+    // the multi-bit blind rotation and bootstrap (multibit_host.hpp): every plan has them, the sums are taken mod p, no size is refused,
+    // and the step works in place on the digits and acc, so the workspace has no scratch.  multibit_step: host_prime_multibit.inc
+    static bool multibit_supported(const Plan *) { return true; }
+    static int multibit_plan_check(const Plan *) { return CNTT_OK; }
+    static bool multibit_sizes_fit(const Plan *, size_t, size_t, unsigned, size_t) { return true; }
+    static int multibit_check_terms(const Plan *, size_t, unsigned, unsigned) { return CNTT_OK; }
+    static constexpr int MAX_LDS_LOGN = MaxLdsLogN<T>::value;
+    static void multibit_scratch(const Plan *, size_t, unsigned, size_t *) {}
+    static int multibit_key_operands(const Plan *, Operand *ops, int cnt, Key bsk, size_t kb) {
+        ops[cnt++] = {"bsk_mb", bsk, kb, sizeof(T), false};
+        return cnt;
+    }
+    static int multibit_step(const Plan *pl, T *acc, T *digits, char *scratch, const MultibitSizes &Z, const uint32_t *rot_rows, Key key,
+                             size_t nterms, size_t npolys, unsigned grouping, size_t batch, hipStream_t st);
 };
 #pragma GCC visibility pop
 

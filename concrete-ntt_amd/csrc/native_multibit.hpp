@@ -3,7 +3,7 @@
 // the NTT domain of prime P_i the monomial is a pointwise factor, so per prime i, element b, output o and word c
 //     out_i[b][o][c] = sum_{t < 2^g} M_i(e_t(b))[c] * ( sum_{j < nterms} terms_i[b][j][c] * key_i[t][j][o][c] )   mod P_i, canonical
 // which is native_multibit_accumulate_kernel, the only kernel of this file.  Digits, residue split, transforms and CRT around it are the
-// stand-alone ones; the loop is host code (host_native_multibit.inc).  Instantiated in native_multibit.hip.  Plan32 kinds only: the
+// stand-alone ones; the loop is host code (multibit_host.hpp; its step: host_native_multibit.inc).  Instantiated in native_multibit.hip.  Plan32 kinds only: the
 // residues are 32-bit words of the ten primes PRIMES32 (host_common.hpp), all below 2^30.
 //
 // It differs from prime_multibit_accumulate_kernel<uint32_t> in three ways.

@@ -2,7 +2,8 @@
 // (include/cntt_prime_pbs.h, host_prime.hip): argument checks, the host-slice staging, the workspace layout and the blind rotation loop.
 // Internal, never installed.  Every function here is a template over a family F, one struct of static members per plan family that supplies
 // what the two differ in and nothing else: NativePbs (host_native_ext.hip) and PrimePbs<T> (host_prime_pbs.inc) show the members.
-// lwe_host.hpp, on top of this file, does the same for the keyswitch, the keyswitch + bootstrap call and the packing keyswitch.
+// lwe_host.hpp, on top of this file, does the same for the keyswitch, the keyswitch + bootstrap call and the packing keyswitch, and
+// multibit_host.hpp for the multi-bit blind rotation and bootstrap.
 #pragma once
 #include "host_common.hpp"
 

@@ -3,7 +3,7 @@
 // formed: in the NTT domain the monomial is a pointwise factor, so
 //     out[b][o][c] = sum_{t < 2^g} M(e_t(b))[c] * ( sum_{j < nterms} terms_ntt[b][j][c] * key[t][j][o][c] )   mod p, canonical
 // which is prime_multibit_accumulate_kernel, the only kernel of this file.  The transforms around it are the stand-alone ones and the digits
-// those of prime_gadget_kernel (prime_pbs.hpp); the loop is host code (host_prime_multibit.inc).  Instantiated in prime_multibit.hip.
+// those of prime_gadget_kernel (prime_pbs.hpp); the loop is host code (multibit_host.hpp; its step: host_prime_multibit.inc).  Instantiated in prime_multibit.hip.
 //
 // The monomial.  With psi the plan's primitive 2n-th root (the forward twiddle at bitrev(1)), fwd(X^e)[c] = psi^(e (2 bitrev_logn(c) + 1)):
 //     M(e)[c] = +-psi^(m mod n),   m = e (2 bitrev(c) + 1) mod 2n,   minus when m >= n        (psi^n = -1)

@@ -5,8 +5,8 @@ multi-bit set-up kernels on their STREAM = true form.  The host picks that form 
     host_prime_automorphism.inc  automorphism_device   2 * polys * n * word                       autom_bytes
     host_prime_automorphism.inc  autoks_device         batch * k * levels * n * word              digit_bytes   (every trace step too)
     host_prime_ring_pack.inc     merge_device          nct * k * levels * n * word                digit_bytes   (nct: the tree level's)
-    host_prime_multibit.inc      multibit_rotate_device      batch * (k + 1) * n * word           acc_bytes
-    host_native_multibit.inc     native_multibit_rotate_device   the same with the native word    acc_bytes
+    multibit_host.hpp            multibit_rotate_device<PrimePbs<T>>  batch * (k + 1) * n * word      acc_bytes
+    multibit_host.hpp            multibit_rotate_device<NativePbs>    the same with the native word   acc_bytes
 
 and returns, for each GPU case, the full call's shape with the bytes of each of its launches, the same at one batch element fewer, the
 shapes of the reference calls with theirs, and the buffers the test holds on the device.  Pure: no GPU, no plan, no state of the

@@ -120,6 +120,26 @@ def test_refusals_are_made_without_a_device():
     assert lwe_out.sum() == 0 and acc.sum() == 0
 
 
+@pytest.mark.parametrize("call", ["blind_rotate_batch", "bootstrap_batch"])
+def test_which_refusal_wins_when_two_arguments_are_wrong(call):
+    """The order of the checks of multibit_host.hpp, which the prime plans share (test_prime_multibit_abi.py has the same cases): the
+    grouping before the divisibility of lwe_dim and before the key, the digit budget before the workspace.  glwe_dim = 1, batch = 1;
+    the pointers are never read."""
+    plan = native64.Plan32.try_new(32)
+    fn, p = plan._fn("multibit_" + call), ctypes.c_void_p
+    args = (p(16), p(16), 0, p(16)) if call == "blind_rotate_batch" else (p(16), p(16), p(16), 0)
+    dummy = (ctypes.c_void_p * plan.NPRIMES)(*[16] * plan.NPRIMES)
+
+    def refusal(key, lwe_dim, base_log, levels, grouping, workspace=None, workspace_bytes=0):
+        rc = fn(plan._h, *args, key, lwe_dim, 1, base_log, levels, grouping, 1, p(workspace), workspace_bytes, 0, None)
+        assert rc == EINVAL
+        return last_error()
+
+    assert refusal(dummy, 4, 4, 2, 5) == "grouping = 5 is not in 1 ... 4"
+    assert refusal(None, 4, 4, 2, 0) == "grouping = 0 is not in 1 ... 4"
+    assert refusal(dummy, 4, 33, 2, 2, workspace=8, workspace_bytes=1 << 20) == "base_log * levels = 33 * 2 exceeds the word width 64"
+
+
 def test_kernel_instance_has_no_scratch_and_no_spills(tmp_path):
     """The gfx950 code object of the new unit: native_multibit_accumulate_kernel, one kernel, without a private segment or a spilled
     register."""

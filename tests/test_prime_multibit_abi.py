@@ -1,6 +1,7 @@
 """C ABI of the prime plans' multi-bit bootstrap (include/cntt_prime_multibit.h): the header is plain C11 and declares the calls, the
 library exports them, cntt.hpp mirrors them, the existing headers keep their surface, the workspace figure is the header's, and the
 code object of the new unit holds the two kernel instances without scratch or spills.  No GPU needed."""
+import ctypes
 import os
 import re
 import subprocess
@@ -9,6 +10,7 @@ import pytest
 
 import concrete_ntt_amd as cntt
 from concrete_ntt_amd import prime32, prime64
+from concrete_ntt_amd._lib import EINVAL, MEM_DEVICE, MEM_HOST, last_error
 from test_prime_pbs_model import P30, P62
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,6 +74,44 @@ def test_workspace_bytes_is_the_formula_of_the_header(mod, p, wb):
     assert getattr(cntt.lib(), "cntt_prime%d_multibit_pbs_workspace_bytes" % (8 * wb))(None, 4, 1, 2, 2, 3) == 0
     grid = cntt.lib().cntt_prime_multibit_grid
     assert grid(0) == 1 and grid(256) == 1 and grid(257) == 2 and grid(1 << 40) == grid(1 << 50)
+
+
+def refusal(plan, call, first, lwe_dim, base_log, levels, grouping, key=16, workspace=None, workspace_bytes=0, where=MEM_HOST, glwe_dim=1):
+    """The message of a refused blind rotation (`first`: acc) or bootstrap (`first`: lwe_out) at the C ABI with batch = 1;
+    the other pointers are never read: every refusal asked for here comes before the first device call and the first host read."""
+    fn, p = plan._fn("multibit_" + call), ctypes.c_void_p
+    args = (p(first), p(16), 0, p(16)) if call == "blind_rotate_batch" else (p(first), p(16), p(16), 0)
+    rc = fn(plan._h, *args, p(key), lwe_dim, glwe_dim, base_log, levels, grouping, 1, p(workspace), workspace_bytes, where, None)
+    assert rc == EINVAL
+    return last_error()
+
+
+@pytest.mark.parametrize("call", ["blind_rotate_batch", "bootstrap_batch"])
+@pytest.mark.parametrize("mod,p,bits", [(prime64, P62, 62), (prime32, P30, 30)])
+def test_which_refusal_wins_when_two_arguments_are_wrong(mod, p, bits, call):
+    """The order of the checks of multibit_host.hpp, which the native plans share (test_native_multibit_abi.py has the same cases): the
+    grouping before the divisibility of lwe_dim and before the key, the digit budget before the workspace."""
+    plan = mod.Plan.try_new(32, p)
+    assert refusal(plan, call, 16, 4, 4, 2, 5) == "grouping = 5 is not in 1 ... 4"
+    assert refusal(plan, call, 16, 4, 4, 2, 0, key=None) == "grouping = 0 is not in 1 ... 4"
+    assert refusal(plan, call, 16, 4, bits // 2 + 1, 2, 2, workspace=8, workspace_bytes=1 << 20) == \
+        "base_log * levels = %d * 2 exceeds the bit length %d of the modulus" % (bits // 2 + 1, bits)
+
+
+def test_blind_rotation_takes_a_workspace_of_the_unrounded_digits():
+    """cntt_prime_multibit.h: the blind rotation needs the digits alone, batch * (glwe_dim + 1) * n * sizeof(word) * levels bytes, NOT
+    rounded up to 256.  A device workspace of exactly that size passes the workspace check (the next refusal, the NULL acc, is the one
+    reported) and one byte less does not.  The shape: the smallest plan, n = 32 of prime32, batch 1, levels 1.  With glwe_dim = 1 the
+    digits take 8 n bytes, a multiple of 256 at every n a plan accepts (n >= 32), so that shape cannot tell the two sizes apart;
+    glwe_dim = 2 is the nearest one that can: 384 bytes against 512."""
+    assert prime32.Plan.try_new(16, P30) is None
+    plan, glwe_dim = prime32.Plan.try_new(32, P30), 2
+    need = 1 * (glwe_dim + 1) * 32 * 4 * 1
+    assert need % 256 == 128 and plan.multibit_pbs_workspace_bytes(4, glwe_dim, 1, 2, 1) > 512
+    ws = dict(workspace=4096, where=MEM_DEVICE, glwe_dim=glwe_dim)
+    assert refusal(plan, "blind_rotate_batch", None, 4, 4, 1, 2, workspace_bytes=need, **ws) == "acc is NULL"
+    assert refusal(plan, "blind_rotate_batch", None, 4, 4, 1, 2, workspace_bytes=need - 1, **ws) == \
+        "workspace_bytes = %d is below the %d bytes this call needs" % (need - 1, need)
 
 
 def test_kernel_instances_have_no_scratch_and_no_spills(tmp_path):
