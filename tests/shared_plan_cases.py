@@ -15,6 +15,9 @@ Batches.  "small": a handful of elements, so that every kernel of the call has f
 streams are co-resident.  "large": 2 * CUs * per_wg + 5 elements, per_wg the elements one workgroup of the family's widest kernel takes
 (4096 / n for the fused products, fewer for the composed calls whose workspace grows with the batch): every grid-stride kernel walks its
 grid more than twice and ends on a ragged round (per_wg = 1 at n = 4096 and 16384, where one element is a workgroup or several).
+In the ring-pack, merge and Galois-keyswitch rows an element is several workgroups of the widest kernel (widest_polys: up to 64 in the
+m = n packing, whose small batch of 3 is 192 workgroups and not below half the CUs); per_wg follows from the exported grid rules, with
+the arithmetic in the comments of those rows and asserted in tests/test_shared_plan_cases.py.
 
 The prime rows cover both word widths and the lazy (P62, P30), strict (P63, P31), doubles (P50, P32) and 2^64 - c (PM64) classes; the
 native rows the 32-, 64- and 128-bit Plan32 kinds and one Plan52 kind on the composed path; "ws" says whether the concurrent calls
@@ -28,6 +31,7 @@ import native_multibit_model as nmm
 import prime_automorphism_model as pam
 import prime_multibit_model as pmm
 import prime_pack_model as ppm
+import prime_ring_pack_model as prm
 import test_prime_pbs_model as pm
 from test_prime_keyswitch_abi import model_keyswitch
 from test_prime_pbs_model import P30, P32, P50, P62, P63, PM64
@@ -51,6 +55,25 @@ ROWS = [
     dict(name="prime_multibit_g2", fam="prime_mb", p=P62, n=64, L=4, k=1, beta=7, ell=3, g=2, small=5, per_wg=8, ws=False),
     dict(name="prime_multibit_g3", fam="prime_mb", p=P32, n=64, L=6, k=1, beta=7, ell=3, g=3, small=5, per_wg=8, ws=True),
     dict(name="prime_trace", fam="prime_trace", p=P31, n=64, steps=3, k=1, beta=7, ell=3, small=5, per_wg=8, ws=False),
+    # The ring-pack, merge and Galois-keyswitch rows.  Their kernels take one workgroup per polynomial up to the cap of the exported grid
+    # rules, cntt_prime_ring_pack_grid and cntt_prime_automorphism_grid: 8 workgroups per CU of a 256-CU part = 2048 at n = 64 on both
+    # word widths.  The widest kernel of a row has E polynomials per batch element (widest_polys), so 2 * 256 * per_wg + 5 elements walk
+    # the grid more than twice as soon as 256 * per_wg * E >= 2048, per_wg = ceil(8 / E), and the 5 further elements leave a ragged round.
+    # E = (m / 2) (k + 1) = 8 in the stage-1 merge (LWE rows as leaves), three stages buf_a -> buf_b -> buf_a, three trace steps with
+    # buf_b idle: per_wg = 1, 517 elements, 4136 workgroups = 2 * 2048 + 40
+    dict(name="prime_ring_pack", fam="prime_ring_pack", p=P62, n=64, m=8, k=1, beta=7, ell=3, small=5, per_wg=1, ws=False),
+    # m = n: no trace, the last merge writes the output.  E = 32 * 2 = 64: per_wg = 1, 517 elements, 33088 workgroups = 16 * 2048 + 320;
+    # the large batch holds 4 * 8.6 MB of LWE rows and one workspace of 25.4 MB per concurrent call.  The model takes 0.2 s per element at m = 64, 3 s for
+    # the three sampled elements of four sets, so the row keeps n = m = 64
+    dict(name="prime_ring_pack_full", fam="prime_ring_pack", p=P32, n=64, m=64, k=1, beta=7, ell=3, small=3, per_wg=1, ws=True),
+    # m = 1: no tree, the embedding into buf_a and the full trace of six steps.  E = k + 1 = 3 (the embedding and every keyswitch of
+    # the trace): per_wg = 3, 1541 elements, 4623 workgroups = 2 * 2048 + 527
+    dict(name="prime_ring_pack_single", fam="prime_ring_pack", p=PM64, n=64, m=1, k=2, beta=7, ell=3, small=5, per_wg=3, ws=False),
+    # one tree node through the public call; the rotation by 101 is past the sign wrap at n and no multiple of the four words of a
+    # 16-byte vector.  E = k + 1 = 2: per_wg = 4, 2053 elements, 4106 workgroups = 2 * 2048 + 10
+    dict(name="prime_merge", fam="prime_merge", p=P30, n=64, shift=101, t=5, k=1, beta=7, ell=3, small=5, per_wg=4, ws=False),
+    # the Galois keyswitch alone, input added, t = n + 1.  E = k + 1 = 3: per_wg = 3, 1541 elements, 4623 workgroups = 2 * 2048 + 527
+    dict(name="prime_autoks", fam="prime_autoks", p=P63, n=64, t=65, k=2, beta=7, ell=3, small=5, per_wg=3, ws=True),
     # -- native plans --------------------------------------------------------------------------------------------------------------------
     dict(name="native_ext_fused", fam="native_ext", kind="native64_plan32", n=1024, J=4, O=2, small=5, per_wg=4, ws=False),
     dict(name="native_ext_16384", fam="native_ext", kind="native32_plan32", n=16384, J=2, O=2, small=3, per_wg=1, ws=False),
@@ -75,6 +98,13 @@ def seed(*parts):
 
 def batch_of(row, regime, ncu):
     return row["small"] if regime == "small" else 2 * ncu * row["per_wg"] + 5
+
+
+def widest_polys(row):
+    """polynomials per batch element in the widest kernel of a ring-pack, merge or Galois-keyswitch row, one workgroup each up to the cap
+    of the exported grid rule: the stage-1 merge of the packing, batch * (m / 2) * (k + 1) (without a tree, m = 1, the embedding and the
+    keyswitches of the trace, batch * (k + 1)); the merge kernel and the keyswitch's gadget kernel, batch * (k + 1)"""
+    return max(row.get("m", 1) // 2, 1) * (row["k"] + 1)
 
 
 def sampled(batch):
@@ -184,8 +214,12 @@ def in_out_words(row, batch):
         return batch * (k * n + 1) * m, (k * n + 1) * m
     if f in ("prime_pack", "native_pack"):
         return batch * row["m"] * (row["lin"] + 1) * m, (k + 1) * n * m
-    if f == "prime_trace":
+    if f in ("prime_trace", "prime_autoks"):
         return batch * (k + 1) * n, (k + 1) * n
+    if f == "prime_ring_pack":
+        return batch * row["m"] * (k * n + 1), (k + 1) * n
+    if f == "prime_merge":                           # glwe_even of the whole batch, then glwe_odd of the whole batch
+        return 2 * batch * (k + 1) * n, (k + 1) * n
     raise KeyError(f)
 
 
@@ -222,6 +256,10 @@ def shared_inputs(row, k=0):
         s["key"] = _nwords(rng, row["kind"], row["lin"] * row["ell"] * (kk + 1) * n)
     elif f == "prime_trace":
         s["key"] = _pwords(rng, row["p"], row["steps"] * kk * row["ell"] * (kk + 1) * n)
+    elif f == "prime_ring_pack":                     # the log2 n trace keys back to back
+        s["key"] = _pwords(rng, row["p"], (n.bit_length() - 1) * kk * row["ell"] * (kk + 1) * n)
+    elif f in ("prime_merge", "prime_autoks"):       # one key
+        s["key"] = _pwords(rng, row["p"], kk * row["ell"] * (kk + 1) * n)
     else:
         raise KeyError(f)
     return s
@@ -372,5 +410,19 @@ def want(oracle, row, shared, one_set, b, batch, k=0):
     if f == "prime_trace":
         p = row["p"]
         out = pam.model_trace(x.tolist(), shared["key"].tolist(), p, row["steps"], row["k"], n, row["beta"], row["ell"])
+        return np.array(out, dtype=pdt(p))
+    if f == "prime_ring_pack":
+        p, m, k = row["p"], row["m"], row["k"]
+        out = prm.model_ring_pack(_chunks(x.tolist(), k * n + 1), shared["key"].tolist(), p, m, k, n, row["beta"], row["ell"])
+        return np.array(out, dtype=pdt(p))
+    if f == "prime_merge":
+        p, k = row["p"], row["k"]
+        ct = (k + 1) * n
+        E, O = (one_set["in"][(h * batch + b) * ct:(h * batch + b + 1) * ct].tolist() for h in range(2))
+        out = prm.model_merge(E, O, shared["key"].tolist(), p, row["shift"], row["t"], k, n, row["beta"], row["ell"])
+        return np.array(out, dtype=pdt(p))
+    if f == "prime_autoks":
+        p = row["p"]
+        out = pam.model_autoks_batch(x.tolist(), shared["key"].tolist(), p, row["t"], row["k"], n, row["beta"], row["ell"], True, 1)
         return np.array(out, dtype=pdt(p))
     raise KeyError(f)

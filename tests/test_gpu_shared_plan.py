@@ -14,7 +14,15 @@ streams.  With REPS = 6, every repetition writing an output of its own and all o
 and passes prime_ext_composed small on two streams (kernels that short finish before the one host thread has enqueued the other
 stream's call; 32 repetitions change nothing) and the 16384 row at its large batch (2 * CUs + 5 elements) both ways.  So each regime
 rejects the defect in at least one of the two tests, neither regime in every row, and a row that passes is weaker evidence about
-ordering than one of those above.  The library as it is passes everything; the same settings run every family."""
+ordering than one of those above.  The library as it is passes everything; the same settings run every family.
+
+The ring-pack rows were calibrated the same way against a second build (not committed): ring_pack (csrc/host_prime_ring_pack.inc)
+taking its digits region and its two ciphertext buffers from one process-wide allocation, made once and larger than any test needs,
+whenever the caller passes no workspace.  With REPS = 6 that build fails
+    prime_ring_pack              small (5 elements) and large (517): two streams and two threads
+    prime_ring_pack_single       small (5 elements) and large (1541): two streams and two threads
+in the first repetition every time, and passes prime_ring_pack_full both ways at both batches, as it must: that row brings one caller
+workspace per concurrent call, which the changed path never sees.  No row needed more repetitions than REPS."""
 import gc
 import threading
 
@@ -120,6 +128,12 @@ def workspace_bytes(row, plan, batch):
         return plan.multibit_pbs_workspace_bytes(row["L"], row["k"], row["ell"], row["g"], batch)
     if f == "prime_trace":
         return plan.glwe_trace_workspace_bytes(row["k"], row["ell"], batch)
+    if f == "prime_ring_pack":
+        return plan.ring_pack_workspace_bytes(row["m"], row["k"], row["ell"], batch)
+    if f == "prime_merge":
+        return plan.glwe_merge_workspace_bytes(row["k"], row["ell"], batch)
+    if f == "prime_autoks":
+        return plan.glwe_automorphism_keyswitch_workspace_bytes(row["k"], row["ell"], batch)
     raise KeyError(f)
 
 
@@ -144,6 +158,15 @@ def launch(row, plan, d, s, out, ws):
         plan.multibit_bootstrap_batch(out, s["in"], d["lut"], d["key"], row["L"], row["k"], row["beta"], row["ell"], row["g"], workspace=ws)
     elif f == "prime_trace":
         plan.glwe_trace_batch(out, s["in"], d["key"], row["steps"], row["k"], row["beta"], row["ell"], workspace=ws)
+    elif f == "prime_ring_pack":
+        plan.ring_pack_batch(out, s["in"], d["key"], row["m"], row["k"], row["beta"], row["ell"], workspace=ws)
+    elif f == "prime_merge":
+        half = s["in"].numel() // 2                                        # glwe_even of the whole batch, then glwe_odd
+        plan.glwe_merge_batch(out, s["in"][:half], s["in"][half:], d["key"], row["shift"], row["t"], row["k"], row["beta"], row["ell"],
+                              workspace=ws)
+    elif f == "prime_autoks":
+        plan.glwe_automorphism_keyswitch_batch(out, s["in"], d["key"], row["t"], row["k"], row["beta"], row["ell"], add_input=True,
+                                               workspace=ws)
     else:
         raise KeyError(f)
 
@@ -314,6 +337,34 @@ def test_first_transform_raced(oracle, p, n):
         y = x.clone()
         plan.fwd_batch(y)
         return y
+
+    race_first_call(torch, tpp.make_plan(p, n), call, inputs,
+                    lambda t, y: np.testing.assert_array_equal(host(y, spc.pdt(p)), want[t], err_msg="thread %d" % t))
+
+
+@gpu
+@pytest.mark.parametrize("p", [spc.P62, spc.P30])
+def test_first_ring_pack_raced(oracle, p):
+    """device_tables again, but built under the race by ring_pack_batch: the plan's first call launches the three tree stages and the
+    three trace steps of the prime_ring_pack shape (n = 64, M = 8, per-call allocation) right behind the upload, seven dependent
+    steps with the embedding.  The keys are transformed on a second plan of the same prime and size, so the plan under test makes no
+    call before the race.  Every thread packs a batch of its own; all words against the model"""
+    import test_gpu_prime_pbs as tpp
+    torch = _torch()
+    row = dict(spc.BY_NAME["prime_ring_pack"], p=p)
+    n, m, k, batch = row["n"], row["m"], row["k"], 3
+    shared = spc.shared_inputs(row)
+    key = tpp.key_ntt(torch, tpp.make_plan(p, n), shared["key"])
+    sets = [spc.set_inputs(row, batch, t) for t in range(FIRST)]
+    per = spc.in_out_words(row, batch)[1]
+    want = [np.concatenate([spc.want(oracle, row, shared, s, b, batch) for b in range(batch)]) for s in sets]
+    inputs = [dev(torch, s["in"]) for s in sets]
+    torch.cuda.synchronize()
+
+    def call(plan, x):
+        out = poisoned(torch, batch * per, spc.pdt(p))
+        plan.ring_pack_batch(out, x, key, m, k, row["beta"], row["ell"])
+        return out
 
     race_first_call(torch, tpp.make_plan(p, n), call, inputs,
                     lambda t, y: np.testing.assert_array_equal(host(y, spc.pdt(p)), want[t], err_msg="thread %d" % t))
