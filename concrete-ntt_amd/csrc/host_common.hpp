@@ -1,5 +1,6 @@
 // What the host units of libcntt_hip.so share (host_core / host_prime / host_native / host_native_ext / host_product .hip): the plan
-// structs behind the C ABI, error reporting, the host-slice staging and the functions that cross unit borders.  Internal, never
+// structs behind the C ABI, error reporting, the memory frame of the _batch calls (Staging: device pointers handed through, host slices
+// staged) and the functions that cross unit borders.  Internal, never
 // installed.  Every __global__ template is launched -- and so instantiated -- by exactly ONE unit; the others call the host function
 // that owns the launch, declared here and explicitly instantiated there.  Nothing declared here is exported.
 // pbs_host.hpp, on top of this file, is the host side of the programmable bootstrap as templates over the plan family, and lwe_host.hpp, on
@@ -82,28 +83,61 @@ inline unsigned ew_grid(size_t work_items) {
 // test_gpu_prime_streaming.py, with the byte count of every launch site that compares against it).
 constexpr size_t STREAM_BYTES = (size_t)384 << 20;
 
-// The host-slice path (CNTT_MEM_HOST) of every call: device copies of the caller's buffers.  in / inout enqueue their host-to-device
-// copy on the stream when they are called; out / inout record a copy back, which finish() enqueues in the order of the calls before
-// the one synchronise.  After a failed allocation or copy every later call returns nullptr and status() / finish() give the code.
-// The device path (CNTT_MEM_DEVICE) never builds one: it allocates nothing here and never synchronises.
+// A stream-ordered device block (hipMallocAsync), released on its stream when the holder goes: after everything the call enqueued
+// before that, on success and on failure alike.  Staging holds its device-mode workspace in one; so do the composed paths' scratch.
+class StreamBlock {
+    hipStream_t st_;
+    void *p_ = nullptr;
+
+  public:
+    explicit StreamBlock(hipStream_t st) : st_(st) {}
+    StreamBlock(const StreamBlock &) = delete;
+    ~StreamBlock() {
+        if (p_) (void)hipFreeAsync(p_, st_);
+    }
+    void *get() const { return p_; }
+    int alloc(size_t bytes) {   // once per holder
+        const hipError_t e = hipMallocAsync(&p_, bytes, st_);
+        if (e == hipSuccess) return CNTT_OK;
+        p_ = nullptr;
+        return fail(CNTT_EDEVICE, "hipMallocAsync(%zu bytes): %s", bytes, hipGetErrorString(e));
+    }
+};
+
+// The memory frame of every _batch call: where its _device function finds the operands and the workspace.  A call states each operand
+// once -- in / out / inout, F::key_in, workspace -- checks status(), runs its _device function on what it got and returns finish().
+// CNTT_MEM_HOST, the host-slice path: device copies of the caller's buffers, one hipMalloc each (16 bytes for an empty one), freed by the
+// destructor.  in / inout enqueue their host-to-device copy on the stream when they are called; out / inout record a copy back, which
+// finish() enqueues in the order of the calls before the one synchronise.  After a failed allocation or copy every later call returns
+// nullptr and status() / finish() give the code.  workspace() is alloc(need): a workspace the caller brought lies in host memory, is
+// checked by the call and then ignored.
+// CNTT_MEM_DEVICE, the device path: in / out / inout hand back the caller's pointer (the NULL of an absent operand too) and allocate,
+// copy and record nothing; finish() is status() and never synchronises.  workspace() is the caller's where there is one -- no runtime
+// call at all then, which is what lets the call sit in a stream capture -- and else, if the call uses it, one hipMallocAsync on the
+// stream that the destructor releases there (StreamBlock).
+// host(): for the two things only the host path may do -- read the rotation exponents (check_rot_host, pbs_host.hpp) and rebuild the
+// native kinds' key planes.
 class Staging {
     struct Back {
         void *host, *dev;
         size_t bytes;
     };
     hipStream_t st_;
+    const bool host_;
     int rc_ = CNTT_OK;
     std::vector<void *> dev_;
     std::vector<Back> back_;
+    StreamBlock ws_;
 
   public:
-    explicit Staging(hipStream_t st) : st_(st) {}
+    Staging(cntt_mem_t where, hipStream_t st) : st_(st), host_(where != CNTT_MEM_DEVICE), ws_(st) {}
     Staging(const Staging &) = delete;
     ~Staging() {
         for (void *p : dev_) (void)hipFree(p);
     }
+    bool host() const { return host_; }
     int status() const { return rc_; }
-    void *alloc(size_t bytes) {   // device scratch that lives as long as this object
+    void *alloc(size_t bytes) {   // host mode: device scratch that lives as long as this object
         void *p = nullptr;
         if (rc_ != CNTT_OK) return nullptr;
         if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) {
@@ -114,23 +148,33 @@ class Staging {
         return p;
     }
     void *in(const void *host, size_t bytes) {
+        if (!host_) return const_cast<void *>(host);
         void *p = alloc(bytes);
         const hipError_t e = p && bytes ? hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, st_) : hipSuccess;
         if (e != hipSuccess) rc_ = fail(CNTT_EDEVICE, "hipMemcpyAsync(host to device, %zu bytes): %s", bytes, hipGetErrorString(e));
         return rc_ == CNTT_OK ? p : nullptr;
     }
     void *out(void *host, size_t bytes) {
+        if (!host_) return host;
         void *p = alloc(bytes);
         if (p && bytes) back_.push_back({host, p, bytes});
         return p;
     }
     void *inout(void *host, size_t bytes) {
+        if (!host_) return host;
         void *p = in(host, bytes);
         if (p && bytes) back_.push_back({host, p, bytes});
         return p;
     }
+    // `used`: whether the call touches its workspace at all (the device path allocates none for a call that does not)
+    void *workspace(void *callers, size_t need, bool used = true) {
+        if (host_) return alloc(need);
+        if (callers || !used || rc_ != CNTT_OK) return callers;
+        rc_ = ws_.alloc(need);
+        return ws_.get();
+    }
     int finish() {
-        if (rc_ != CNTT_OK) return rc_;
+        if (rc_ != CNTT_OK || !host_) return rc_;
         for (const Back &b : back_) HIP_TRY(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, st_));
         HIP_TRY(hipStreamSynchronize(st_));
         return CNTT_OK;

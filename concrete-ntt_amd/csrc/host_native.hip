@@ -443,10 +443,9 @@ static int native_op(const cntt_native *pl, int op, void *value, void *const *re
         for (int i = 0; i < k; ++i) ops[1 + i] = {PLANE[i], res[i], rb, pl->rbytes(), true};
         if (int rc = check_operands(ops, 1 + k)) return rc;
     }
-    if (where == CNTT_MEM_DEVICE) return native_op_device(pl, op, value, res, batch, st);
     // fwd reads the value and writes the residues; inv reads the residues and writes the value AND the (inverse-transformed)
     // residues: src/native64.rs:1010-1014
-    Staging s(st);
+    Staging s(where, st);
     void *dres[10];
     for (int i = 0; i < k; ++i) dres[i] = op == 2 ? s.inout(res[i], rb) : s.out(res[i], rb);
     void *dv = op == 2 ? s.out(value, vbytes) : s.in(value, vbytes);
@@ -615,8 +614,7 @@ extern "C" int cntt_native_negacyclic_polymul_batch(const cntt_native_t *pl, voi
     const size_t vbytes = batch * pl->n * (size_t)pl->info.word, word = (size_t)pl->info.word;
     const Operand ops[3] = {{"prod", prod, vbytes, word, true}, {"lhs", lhs, vbytes, word, false}, {"rhs", rhs, vbytes, word, false}};
     if (int rc = check_operands(ops, 3)) return rc;
-    if (where == CNTT_MEM_DEVICE) return native_polymul_device(pl, prod, lhs, rhs, batch, st);
-    Staging s(st);
+    Staging s(where, st);
     void *dp = s.out(prod, vbytes);
     const void *dl = s.in(lhs, vbytes), *dr = s.in(rhs, vbytes);
     if (int rc = s.status()) return rc;

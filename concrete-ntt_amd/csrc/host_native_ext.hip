@@ -62,8 +62,9 @@ static int native_ext_composed(const cntt_native *pl, void *out, const void *ter
     const size_t n = pl->n, rb = pl->rbytes(), tcount = batch * nterms * n, ocount = batch * nout * n;
     const size_t wbytes = (size_t)pl->info.word;
     const size_t bytes = (size_t)k * (tcount + ocount) * rb + (accumulate ? ocount * wbytes : 0);
-    char *scratch = nullptr;
-    HIP_TRY(hipMallocAsync((void **)&scratch, bytes, st));
+    StreamBlock block(st);
+    if (int rc = block.alloc(bytes)) return rc;
+    char *scratch = (char *)block.get();
     void *T[10], *O[10];
     for (int i = 0; i < k; ++i) {
         T[i] = scratch + (size_t)i * tcount * rb;
@@ -86,7 +87,6 @@ static int native_ext_composed(const cntt_native *pl, void *out, const void *ter
     }
     if (rc == CNTT_OK) rc = native_crt_device(pl, crt_out, O, ocount, st);
     if (rc == CNTT_OK && accumulate) rc = word_add_launch(pl, out, crt_out, ocount, st);
-    (void)hipFreeAsync(scratch, st);
     return rc;
 }
 
@@ -111,7 +111,8 @@ static int check_key_planes(const cntt_native *pl, const void *const *key, const
     }
     return CNTT_OK;
 }
-// host path: their device copies, `bytes` each (no bytes: `key` itself may be NULL)
+// the planes as the _device functions take them: the caller's pointers (device path) or device copies of `bytes` each (host path);
+// no bytes: `key` itself may be NULL
 static void key_planes_to_device(const cntt_native *pl, Staging &s, const void *const *key, size_t bytes, const void **dkey) {
     for (int i = 0; i < pl->info.nprimes; ++i) dkey[i] = s.in(bytes ? key[i] : nullptr, bytes);
 }
@@ -130,9 +131,8 @@ extern "C" int cntt_native_external_product_batch(const cntt_native_t *pl, void 
         if (int rc = check_key_planes(pl, key_ntt, nullptr)) return rc;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (where == CNTT_MEM_DEVICE) return native_ext_device(pl, out, terms, key_ntt, nterms, nout, batch, accumulate != 0, st);
     const size_t n = pl->n, w = (size_t)pl->info.word, ob = batch * nout * n * w, tb = batch * nterms * n * w;
-    Staging s(st);
+    Staging s(where, st);
     const void *dkey[10];
     key_planes_to_device(pl, s, key_ntt, nterms * nout * n * pl->rbytes(), dkey);
     void *dout = accumulate ? s.inout(out, ob) : s.out(out, ob);
@@ -340,13 +340,11 @@ static int native_ext_gadget_device(const cntt_native *pl, void *out, const void
     const int rc = native_ext_gadget_fused(pl, out, G, key, nout, batch, st);
     if (rc != FUSED_NONE) return rc;
     // composed: the digits into stream-ordered scratch, the external product on them, then the addend
-    char *scratch = nullptr;
-    HIP_TRY(hipMallocAsync((void **)&scratch, batch * nterms * n * w, st));
-    int rc2 = native_gadget_device(pl, scratch, polys, rot, npolys, base_log, levels, mode, batch, st);
-    if (rc2 == CNTT_OK) rc2 = native_ext_device(pl, out, scratch, key, nterms, nout, batch, addend == out, st);
-    if (rc2 == CNTT_OK && addend && addend != out) rc2 = word_add_launch(pl, out, addend, ocount, st);
-    (void)hipFreeAsync(scratch, st);
-    return rc2;
+    StreamBlock digits(st);
+    if (int rc2 = digits.alloc(batch * nterms * n * w)) return rc2;
+    if (int rc2 = native_gadget_device(pl, digits.get(), polys, rot, npolys, base_log, levels, mode, batch, st)) return rc2;
+    if (int rc2 = native_ext_device(pl, out, digits.get(), key, nterms, nout, batch, addend == out, st)) return rc2;
+    return addend && addend != out ? word_add_launch(pl, out, addend, ocount, st) : CNTT_OK;
 }
 
 extern "C" int cntt_native_external_product_decomposed_batch(const cntt_native_t *pl, void *out, const void *polys, const uint32_t *rot,
@@ -369,12 +367,10 @@ extern "C" int cntt_native_external_product_decomposed_batch(const cntt_native_t
     }
     if (addend && addend != out && ranges_overlap(out, ob, addend, ob)) return fail(CNTT_EINVAL, "addend overlaps out without being out");
     hipStream_t st = (hipStream_t)stream;
-    if (where == CNTT_MEM_DEVICE)
-        return native_ext_gadget_device(pl, out, polys, rot, addend, key_ntt, npolys, base_log, levels, (int)src_mode, nout, batch, st);
     const bool rotated = nterms && src_mode != CNTT_SRC_PLAIN;
-    if (rotated)
+    Staging s(where, st);
+    if (s.host() && rotated)
         if (int rc = check_rot_host(pl->n, rot, batch, "rot")) return rc;
-    Staging s(st);
     const void *dkey[10];
     key_planes_to_device(pl, s, key_ntt, nterms * nout * n * pl->rbytes(), dkey);
     const void *dp = s.in(polys, pb);

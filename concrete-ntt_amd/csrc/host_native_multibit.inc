@@ -133,9 +133,9 @@ static int native_multibit_accumulate(const cntt_native *pl, void *const *out, c
     for (int i = 0; i < k && nterms; ++i) ops[cnt++] = {MB_KEY[i], key[i], kb, sizeof(uint32_t), false};
     ops[cnt++] = {"rot_rows", rot_rows, rb, sizeof(uint32_t), false};
     if (int rc = check_operands(ops, cnt)) return rc;
-    if (where == CNTT_MEM_DEVICE) return native_multibit_accumulate_device(pl, out, terms, rot_rows, key, nterms, nout, grouping, batch, st);
-    if (int rc = check_rot_host(pl->n, rot_rows, grouping * batch, "rot_rows")) return rc;
-    Staging s(st);
+    Staging s(where, st);
+    if (s.host())
+        if (int rc = check_rot_host(pl->n, rot_rows, grouping * batch, "rot_rows")) return rc;
     void *dout[10];
     const void *dt[10], *dk[10];
     for (int i = 0; i < k; ++i) {

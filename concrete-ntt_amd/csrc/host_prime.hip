@@ -378,27 +378,16 @@ int external_product_device(const PrimePlan<T> *pl, T *out, const T *terms, cons
     if (e != hipErrorNotSupported) return fail(CNTT_EDEVICE, "fused mul_accumulate chain launch failed: %s", hipGetErrorString(e));
     (void)hipGetLastError();
     const size_t tw = batch * nterms * n, ow = batch * nout * n;
-    T *scratch = nullptr;
-    HIP_TRY(hipMallocAsync((void **)&scratch, (tw + (accumulate ? ow : 0)) * sizeof(T), st));
-    T *tn = scratch, *acc = accumulate ? scratch + tw : out;
-    int rc = CNTT_OK;
-    do {
-        if (hipMemcpyAsync(tn, terms, tw * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-            rc = fail(CNTT_EDEVICE, "device copy failed");
-            break;
-        }
-        if ((rc = ntt_device<T>(pl, tn, batch * nterms, false, st))) break;
-        hipLaunchKernelGGL((ext_accumulate_kernel<T>), dim3(ew_grid(ow / (16 / sizeof(T)))), dim3(256), 0, st, acc, tn, key,
-                           pl->mp, (uint32_t)pl->logn, (uint32_t)nterms, (uint32_t)nout, batch);
-        if (hipGetLastError() != hipSuccess) {
-            rc = fail(CNTT_EDEVICE, "ext_accumulate_kernel launch failed");
-            break;
-        }
-        if ((rc = ntt_device<T>(pl, acc, batch * nout, true, st))) break;
-        if (accumulate) rc = pointwise_device<T, PW_ADD>(pl, out, acc, nullptr, ow, st);
-    } while (false);
-    (void)hipFreeAsync(scratch, st);
-    return rc;
+    StreamBlock scratch(st);
+    if (int rc = scratch.alloc((tw + (accumulate ? ow : 0)) * sizeof(T))) return rc;
+    T *tn = (T *)scratch.get(), *acc = accumulate ? tn + tw : out;
+    if (hipMemcpyAsync(tn, terms, tw * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CNTT_EDEVICE, "device copy failed");
+    if (int rc = ntt_device<T>(pl, tn, batch * nterms, false, st)) return rc;
+    hipLaunchKernelGGL((ext_accumulate_kernel<T>), dim3(ew_grid(ow / (16 / sizeof(T)))), dim3(256), 0, st, acc, tn, key,
+                       pl->mp, (uint32_t)pl->logn, (uint32_t)nterms, (uint32_t)nout, batch);
+    if (hipGetLastError() != hipSuccess) return fail(CNTT_EDEVICE, "ext_accumulate_kernel launch failed");
+    if (int rc = ntt_device<T>(pl, acc, batch * nout, true, st)) return rc;
+    return accumulate ? pointwise_device<T, PW_ADD>(pl, out, acc, nullptr, ow, st) : CNTT_OK;
 }
 
 template <class T>
@@ -410,8 +399,7 @@ static int external_product(const PrimePlan<T> *pl, T *out, const T *terms, cons
     const size_t n = pl->n, ob = batch * nout * n * sizeof(T), tb = batch * nterms * n * sizeof(T), kb = nterms * nout * n * sizeof(T);
     const Operand ops[3] = {{"out", out, ob, sizeof(T), true}, {"terms", terms, tb, sizeof(T), false}, {"key_ntt", key, kb, sizeof(T), false}};
     if (int rc = check_operands(ops, 3)) return rc;
-    if (where == CNTT_MEM_DEVICE) return external_product_device<T>(pl, out, terms, key, nterms, nout, batch, accumulate != 0, st);
-    Staging s(st);
+    Staging s(where, st);
     T *dout = (T *)(accumulate ? s.inout(out, ob) : s.out(out, ob));
     const T *dt = (const T *)s.in(terms, tb), *dk = (const T *)s.in(key, kb);
     if (int rc = s.status()) return rc;
@@ -420,6 +408,17 @@ static int external_product(const PrimePlan<T> *pl, T *out, const T *terms, cons
 }
 
 // op: 0 fwd, 1 inv, 2 mul_assign_normalize, 3 normalize, 4 mul_accumulate, 5 mul_ntt ; count = total elements
+template <class T>
+static int prime_op_device(const PrimePlan<T> *pl, int op, T *a, const T *b, const T *c, size_t count, size_t batch, hipStream_t st) {
+    switch (op) {
+    case 0: return ntt_device<T>(pl, a, batch, false, st);
+    case 1: return ntt_device<T>(pl, a, batch, true, st);
+    case 2: return pointwise_device<T, PW_MUL_NORMALIZE>(pl, a, b, nullptr, count, st);
+    case 3: return pointwise_device<T, PW_NORMALIZE>(pl, a, nullptr, nullptr, count, st);
+    case 5: return mul_ntt_device<T>(pl, a, b, batch, st);
+    default: return pointwise_device<T, PW_MUL_ACCUMULATE>(pl, a, b, c, count, st);
+    }
+}
 template <class T>
 static int prime_op(const PrimePlan<T> *pl, int op, T *a, const T *b, const T *c, size_t count, size_t batch,
                     cntt_mem_t where, hipStream_t st) {
@@ -433,24 +432,13 @@ static int prime_op(const PrimePlan<T> *pl, int op, T *a, const T *b, const T *c
                                 {NAMES[op][2], c, c ? count * sizeof(T) : 0, sizeof(T), false}};
         if (int rc = check_operands(ops, 3)) return rc;
     }
-    auto run = [&](T *da, const T *db, const T *dc) -> int {
-        switch (op) {
-        case 0: return ntt_device<T>(pl, da, batch, false, st);
-        case 1: return ntt_device<T>(pl, da, batch, true, st);
-        case 2: return pointwise_device<T, PW_MUL_NORMALIZE>(pl, da, db, nullptr, count, st);
-        case 3: return pointwise_device<T, PW_NORMALIZE>(pl, da, nullptr, nullptr, count, st);
-        case 5: return mul_ntt_device<T>(pl, da, db, batch, st);
-        default: return pointwise_device<T, PW_MUL_ACCUMULATE>(pl, da, db, dc, count, st);
-        }
-    };
-    if (where == CNTT_MEM_DEVICE) return run(a, b, c);
     const size_t bytes = count * sizeof(T);
-    Staging s(st);
+    Staging s(where, st);
     T *da = (T *)s.inout(a, bytes);
     const T *db = op == 2 || op == 4 || op == 5 ? (const T *)s.in(b, bytes) : nullptr;
     const T *dc = op == 4 ? (const T *)s.in(c, bytes) : nullptr;
     if (int rc = s.status()) return rc;
-    if (int rc = run(da, db, dc)) return rc;
+    if (int rc = prime_op_device<T>(pl, op, da, db, dc, count, batch, st)) return rc;
     return s.finish();
 }
 

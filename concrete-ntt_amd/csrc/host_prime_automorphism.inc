@@ -38,8 +38,7 @@ static int automorphism(const PrimePlan<T> *pl, T *out, const T *in, size_t t, s
     const size_t polys = batch * npolys, bytes = polys * pl->n * sizeof(T);
     const Operand ops[2] = {{on, out, bytes, sizeof(T), true}, {in_name, in, bytes, sizeof(T), false}};
     if (int rc = check_operands(ops, 2)) return rc;
-    if (where == CNTT_MEM_DEVICE) return automorphism_device<T>(pl, out, in, t, ntt, polys, st);
-    Staging s(st);
+    Staging s(where, st);
     T *dout = (T *)s.out(out, bytes);
     const T *din = (const T *)s.in(in, bytes);
     if (int rc = s.status()) return rc;
@@ -126,27 +125,16 @@ static int glwe_autoks(const PrimePlan<T> *pl, T *glwe_out, const T *glwe_in, co
                             {"ak_ntt", ak_ntt, kb, sizeof(T), false},
                             {"workspace", workspace, workspace ? workspace_bytes : 0, 16, true}};
     if (int rc = check_operands(ops, 4)) return rc;
-    auto run = [&](T *out, const T *in, const T *ak, char *ws) {
-        T *terms = static_cast<T *>(static_cast<void *>(ws));
-        if (!trace) return autoks_device<T>(pl, out, in, ak, t, k, base_log, levels, add_input, batch, terms, st);
-        T *tmp = ws ? static_cast<T *>(static_cast<void *>(ws + digits)) : nullptr;
-        return trace_device<T>(pl, out, in, ak, steps, k, base_log, levels, batch, terms, tmp, st);
-    };
-    // what the call touches of the workspace: nothing without a step, the digits with a key, the second ciphertext from two steps on
-    const bool wants_ws = steps > 0 && (k > 0 || (trace && steps > 1));
-    if (where == CNTT_MEM_DEVICE) {
-        void *ws = workspace;
-        if (!ws && wants_ws) HIP_TRY(hipMallocAsync(&ws, need, st));   // one allocation for the whole call
-        const int rc = run(glwe_out, glwe_in, ak_ntt, static_cast<char *>(ws));
-        if (!workspace && ws) (void)hipFreeAsync(ws, st);
-        return rc;
-    }
-    Staging s(st);
+    Staging s(where, st);
     const T *din = (const T *)s.in(glwe_in, cb), *dak = keyed ? (const T *)s.in(ak_ntt, kb) : nullptr;
     T *dout = (T *)s.out(glwe_out, cb);
-    char *dws = (char *)s.alloc(need);
+    // what the call touches of the workspace: nothing without a step, the digits with a key, the second ciphertext from two steps on
+    char *dws = (char *)s.workspace(workspace, need, steps > 0 && (k > 0 || (trace && steps > 1)));   // one block for the whole call
     if (int rc = s.status()) return rc;
-    if (int rc = run(dout, din, dak, dws)) return rc;
+    T *terms = static_cast<T *>(static_cast<void *>(dws)), *tmp = dws ? static_cast<T *>(static_cast<void *>(dws + digits)) : nullptr;
+    if (int rc = trace ? trace_device<T>(pl, dout, din, dak, steps, k, base_log, levels, batch, terms, tmp, st)
+                       : autoks_device<T>(pl, dout, din, dak, t, k, base_log, levels, add_input, batch, terms, st))
+        return rc;
     return s.finish();
 }
 #pragma GCC visibility pop

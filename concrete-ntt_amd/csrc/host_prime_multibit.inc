@@ -92,9 +92,9 @@ static int multibit_accumulate(const PrimePlan<T> *pl, T *out, const T *terms, c
                             {"rot_rows", rot_rows, rb, sizeof(uint32_t), false},
                             {"key_group", key, kb, sizeof(T), false}};
     if (int rc = check_operands(ops, 4)) return rc;
-    if (where == CNTT_MEM_DEVICE) return multibit_accumulate_device<T>(pl, out, terms, rot_rows, key, nterms, nout, grouping, batch, st);
-    if (int rc = check_rot_host(pl->n, rot_rows, grouping * batch, "rot_rows")) return rc;
-    Staging s(st);
+    Staging s(where, st);
+    if (s.host())
+        if (int rc = check_rot_host(pl->n, rot_rows, grouping * batch, "rot_rows")) return rc;
     T *dout = (T *)s.out(out, ob);
     const T *dt = (const T *)s.in(terms, tb), *dk = (const T *)s.in(key, kb);
     const uint32_t *dr = (const uint32_t *)s.in(rot_rows, rb);

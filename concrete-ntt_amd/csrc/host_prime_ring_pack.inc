@@ -60,8 +60,7 @@ template <class T> static int glwe_embed(const PrimePlan<T> *pl, T *glwe_out, co
     const size_t gb = batch * (k + 1) * pl->n * sizeof(T), lb = batch * (k * pl->n + 1) * sizeof(T);
     const Operand ops[2] = {{"glwe_out", glwe_out, gb, sizeof(T), true}, {"lwe_in", lwe_in, lb, sizeof(T), false}};
     if (int rc = check_operands(ops, 2)) return rc;
-    if (where == CNTT_MEM_DEVICE) return embed_device<T>(pl, glwe_out, lwe_in, k, batch, st);
-    Staging s(st);
+    Staging s(where, st);
     T *dout = (T *)s.out(glwe_out, gb);
     const T *din = (const T *)s.in(lwe_in, lb);
     if (int rc = s.status()) return rc;
@@ -95,22 +94,12 @@ static int glwe_merge(const PrimePlan<T> *pl, T *glwe_out, const T *even, const 
                             {"ak_ntt", ak_ntt, kb, sizeof(T), false},
                             {"workspace", workspace, workspace ? workspace_bytes : 0, 16, true}};
     if (int rc = check_operands(ops, 5)) return rc;
-    auto run = [&](T *out, const T *e, const T *o, const T *ak, void *ws) {
-        return merge_device<T>(pl, out, e, o, false, ak, shift, t, k, base_log, levels, 1, 1, batch, static_cast<T *>(ws), st);
-    };
-    if (where == CNTT_MEM_DEVICE) {
-        void *ws = workspace;
-        if (!ws && k > 0) HIP_TRY(hipMallocAsync(&ws, need, st));   // one allocation for the whole call
-        const int rc = run(glwe_out, even, odd, ak_ntt, ws);
-        if (!workspace && ws) (void)hipFreeAsync(ws, st);
-        return rc;
-    }
-    Staging s(st);
+    Staging s(where, st);
     const T *de = (const T *)s.in(even, cb), *dod = (const T *)s.in(odd, cb), *dak = k > 0 ? (const T *)s.in(ak_ntt, kb) : nullptr;
     T *dout = (T *)s.out(glwe_out, cb);
-    void *dws = s.alloc(need);
+    T *dterms = (T *)s.workspace(workspace, need, k > 0);   // one block for the whole call
     if (int rc = s.status()) return rc;
-    if (int rc = run(dout, de, dod, dak, dws)) return rc;
+    if (int rc = merge_device<T>(pl, dout, de, dod, false, dak, shift, t, k, base_log, levels, 1, 1, batch, dterms, st)) return rc;
     return s.finish();
 }
 
@@ -176,25 +165,15 @@ static int ring_pack(const PrimePlan<T> *pl, T *glwe_out, const T *lwe_in, const
                             {"ak_ntt", ak_ntt, kb, sizeof(T), false},
                             {"workspace", workspace, workspace ? workspace_bytes : 0, 16, true}};
     if (int rc = check_operands(ops, 4)) return rc;
-    auto run = [&](T *out, const T *lwe, const T *ak, char *ws) {
-        T *terms = static_cast<T *>(static_cast<void *>(ws));
-        T *buf_a = static_cast<T *>(static_cast<void *>(ws + up256(Z.digits)));
-        T *buf_b = static_cast<T *>(static_cast<void *>(ws + up256(Z.digits) + up256(Z.buf_a)));
-        return ring_pack_device<T>(pl, out, lwe, ak, m, k, base_log, levels, batch, terms, buf_a, buf_b, st);
-    };
-    if (where == CNTT_MEM_DEVICE) {
-        void *ws = workspace;
-        if (!ws) HIP_TRY(hipMallocAsync(&ws, need, st));   // one allocation for the whole call
-        const int rc = run(glwe_out, lwe_in, ak_ntt, static_cast<char *>(ws));
-        if (!workspace) (void)hipFreeAsync(ws, st);
-        return rc;
-    }
-    Staging s(st);
+    Staging s(where, st);
     const T *din = (const T *)s.in(lwe_in, ib), *dak = k > 0 ? (const T *)s.in(ak_ntt, kb) : nullptr;
     T *dout = (T *)s.out(glwe_out, ob);
-    char *dws = (char *)s.alloc(need);
+    char *dws = (char *)s.workspace(workspace, need);   // one block for the whole call
     if (int rc = s.status()) return rc;
-    if (int rc = run(dout, din, dak, dws)) return rc;
+    T *terms = static_cast<T *>(static_cast<void *>(dws));
+    T *buf_a = static_cast<T *>(static_cast<void *>(dws + up256(Z.digits)));
+    T *buf_b = static_cast<T *>(static_cast<void *>(dws + up256(Z.digits) + up256(Z.buf_a)));
+    if (int rc = ring_pack_device<T>(pl, dout, din, dak, m, k, base_log, levels, batch, terms, buf_a, buf_b, st)) return rc;
     return s.finish();
 }
 #pragma GCC visibility pop

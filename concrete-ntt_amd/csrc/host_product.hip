@@ -240,9 +240,9 @@ static int product_external_product_device(const cntt_product *pl, uint64_t *out
         // chain reads `terms` and writes `out` directly -- no residue buffers at all
         return external_product_device<uint64_t>(pl->p64[0].get(), out, terms, key, nterms, nout, batch, accumulate, st);
     const size_t tpolys = batch * nterms, opolys = batch * nout, kpolys = nterms * nout;
-    uint64_t *scratch = nullptr;
-    HIP_TRY(hipMallocAsync((void **)&scratch, (tpolys + opolys) * dl * 8, st));
-    uint64_t *tres = scratch, *ores = scratch + tpolys * dl;
+    StreamBlock scratch(st);
+    if (int rc = scratch.alloc((tpolys + opolys) * dl * 8)) return rc;
+    uint64_t *tres = (uint64_t *)scratch.get(), *ores = tres + tpolys * dl;
     const ProductView tv = product_view(pl, tres, tpolys), ov = product_view(pl, ores, opolys);
     const ProductView kv = product_view(pl, const_cast<uint64_t *>(key), kpolys);
     int rc = product_split_device(pl, tv, terms, tpolys, bounded, bound, st);
@@ -253,7 +253,6 @@ static int product_external_product_device(const cntt_product *pl, uint64_t *out
         rc = external_product_device<uint64_t>(pl->p64[i].get(), ov.r64 + i * opolys * n, tv.r64 + i * tpolys * n,
                                                kv.r64 + i * kpolys * n, nterms, nout, batch, false, st);
     if (rc == CNTT_OK) rc = product_crt_device(pl, out, ov, opolys, accumulate, st);
-    (void)hipFreeAsync(scratch, st);
     return rc;
 }
 
@@ -302,23 +301,18 @@ static int product_op(const cntt_product *pl, int op, uint64_t *a, uint64_t *b, 
                                 {NAMES[op][2], c, op == 4 ? dom_words * 8 : 0, 8, false}};
         if (int rc = check_operands(ops, 3)) return rc;
     }
-    auto run = [&](uint64_t *da, uint64_t *db, const uint64_t *dc) -> int {
-        switch (op) {
-        case 0: return product_fwd_device(pl, da, db, batch, mode != 0, bound, st);
-        case 1: return product_inv_device(pl, da, db, batch, mode != 0, st);
-        default: return product_pointwise_device(pl, op, da, db, dc, batch, st);
-        }
-    };
-    if (where == CNTT_MEM_DEVICE) return run(a, b, c);
     // a: read unless the op only writes it (fwd; inv replacing), written back unless inv accumulates onto it with no primes at all
     const bool a_in = op != 0 && !(op == 1 && mode == 0), a_out = !(op == 1 && mode != 0 && pl->primes.empty());
-    Staging s(st);
+    Staging s(where, st);
     uint64_t *da = (uint64_t *)(a_in && a_out ? s.inout(a, aw * 8) : a_in ? s.in(a, aw * 8) : s.out(a, aw * 8));
     // inv leaves the inverse-transformed residues in the caller's ntt buffer: src/product.rs:368-373
     uint64_t *db = (uint64_t *)(op == 3 ? nullptr : op == 1 ? s.inout(b, bw * 8) : s.in(b, bw * 8));
     const uint64_t *dc = op == 4 ? (const uint64_t *)s.in(c, dom_words * 8) : nullptr;
     if (int rc = s.status()) return rc;
-    if (int rc = run(da, db, dc)) return rc;
+    if (int rc = op == 0   ? product_fwd_device(pl, da, db, batch, mode != 0, bound, st)
+                 : op == 1 ? product_inv_device(pl, da, db, batch, mode != 0, st)
+                           : product_pointwise_device(pl, op, da, db, dc, batch, st))
+        return rc;
     return s.finish();
 }
 
@@ -394,9 +388,7 @@ extern "C" int cntt_product_external_product_batch(const cntt_product_t *pl, uin
     const size_t ob = batch * nout * n * 8, tb = batch * nterms * n * 8, kb = nterms * nout * dl * 8;
     const Operand ops[3] = {{"out", out, ob, 8, true}, {"terms", terms, tb, 8, false}, {"key_ntt", key_ntt, kb, 8, false}};
     if (int rc = check_operands(ops, 3)) return rc;
-    if (where == CNTT_MEM_DEVICE)
-        return product_external_product_device(pl, out, terms, key_ntt, nterms, nout, batch, bounded, bound, accumulate, st);
-    Staging s(st);
+    Staging s(where, st);
     uint64_t *dout = (uint64_t *)(accumulate ? s.inout(out, ob) : s.out(out, ob));
     const uint64_t *dt = (const uint64_t *)s.in(terms, tb), *dk = (const uint64_t *)s.in(key_ntt, kb);
     if (int rc = s.status()) return rc;

@@ -1,7 +1,7 @@
 // The host side of what works on LWE ciphertexts around the bootstrap, once for the native plans (include/cntt_keyswitch.h, cntt_pack.h;
 // host_native_ext.hip) and the prime plans (include/cntt_prime_keyswitch.h, cntt_prime_pack.h; host_prime.hip): the LWE keyswitch, the
-// keyswitch + bootstrap call and the LWE-to-GLWE packing keyswitch -- argument checks, the host-slice staging, the workspace layout and
-// the chunk loop.  Internal, never installed.  Templates over a family F as in pbs_host.hpp, which this file builds on: the bootstrap
+// keyswitch + bootstrap call and the LWE-to-GLWE packing keyswitch -- argument checks, the workspace layout and the chunk loop, each
+// call on one path for device pointers and host slices through Staging (host_common.hpp).  Internal, never installed.  Templates over a family F as in pbs_host.hpp, which this file builds on: the bootstrap
 // family plus the members the second half of NativePbs (host_native_ext.hip) and PrimeKs<T> / PrimePack<T> (host_prime_keyswitch.inc,
 // host_prime_pack.inc) show.
 #pragma once
@@ -55,9 +55,7 @@ int keyswitch(const typename F::Plan *pl, typename F::Word *lwe_out, const typen
     const size_t kb = ksk_bytes<F>(pl, lwe_dim_in * levels, lwe_dim_out, row_stride);
     if (ranges_overlap(lwe_out, ob, lwe_in, ib)) return fail(CNTT_EINVAL, "lwe_out overlaps lwe_in");
     if (ranges_overlap(lwe_out, ob, ksk, kb)) return fail(CNTT_EINVAL, "lwe_out overlaps ksk");
-    if (where == CNTT_MEM_DEVICE)
-        return keyswitch_device<F>(pl, lwe_out, lwe_in, ksk, lwe_dim_in, lwe_dim_out, row_stride, base_log, levels, batch, st);
-    Staging s(st);
+    Staging s(where, st);
     W *dout = (W *)s.out(lwe_out, ob);
     const W *din = (const W *)s.in(lwe_in, ib), *dk = (const W *)s.in(ksk, kb);
     if (int rc = s.status()) return rc;
@@ -103,28 +101,19 @@ int keyswitch_bootstrap(const typename F::Plan *pl, typename F::Word *lwe_out, c
         if (ranges_overlap(ksk, kb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "ksk overlaps workspace");
         if (ranges_overlap(lut, lb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lut overlaps workspace");
     }
-    // keyswitch into the tail of the workspace, bootstrap from there with the head
-    auto run = [&](W *out, const W *in, const W *key, const W *table, typename F::Key bkey, char *ws) {
-        W *lwe_mid = static_cast<W *>(static_cast<void *>(ws + Z.total()));
-        if (int rc = keyswitch_device<F>(pl, lwe_mid, in, key, big, lwe_dim, row_stride, ks_base_log, ks_levels, batch, st)) return rc;
-        return bootstrap_device<F>(pl, out, lwe_mid, table, lut_per_element != 0, bkey, lwe_dim, glwe_dim, base_log, levels, batch, Z, ws, st);
-    };
-    if (where == CNTT_MEM_DEVICE) {
-        void *ws = workspace;
-        if (!ws) HIP_TRY(hipMallocAsync(&ws, need, st));   // one allocation for the whole call
-        const int rc = run(lwe_out, lwe_in, ksk, lut, bsk, static_cast<char *>(ws));
-        if (!workspace) (void)hipFreeAsync(ws, st);
-        return rc;
-    }
     const size_t bb = F::key_bytes(pl, lwe_dim * (glwe_dim + 1) * levels * (glwe_dim + 1));
-    Staging s(st);
+    Staging s(where, st);
     typename F::KeyStore ks;
     const typename F::Key dkey = lwe_dim ? F::key_in(pl, s, bsk, bb, ks) : typename F::Key{};
     const W *din = (const W *)s.in(lwe_in, eb), *dk = (const W *)s.in(ksk, kb), *dlut = (const W *)s.in(lut, lb);
     W *dout = (W *)s.out(lwe_out, eb);
-    char *dws = (char *)s.alloc(need);
+    char *dws = (char *)s.workspace(workspace, need);   // one block for the whole call
     if (int rc = s.status()) return rc;
-    if (int rc = run(dout, din, dk, dlut, dkey, dws)) return rc;
+    // keyswitch into the tail of the workspace, bootstrap from there with the head
+    W *lwe_mid = static_cast<W *>(static_cast<void *>(dws + Z.total()));
+    if (int rc = keyswitch_device<F>(pl, lwe_mid, din, dk, big, lwe_dim, row_stride, ks_base_log, ks_levels, batch, st)) return rc;
+    if (int rc = bootstrap_device<F>(pl, dout, lwe_mid, dlut, lut_per_element != 0, dkey, lwe_dim, glwe_dim, base_log, levels, batch, Z, dws, st))
+        return rc;
     return s.finish();
 }
 
@@ -187,18 +176,11 @@ int pack_keyswitch(const typename F::Plan *pl, typename F::Word *glwe_out, const
         if (ranges_overlap(glwe_out, ob, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "glwe_out overlaps workspace");
         if (ranges_overlap(lwe_in, ib, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_in overlaps workspace");
     }
-    if (where == CNTT_MEM_DEVICE) {
-        void *terms = workspace;
-        if (!terms && lwe_dim_in) HIP_TRY(hipMallocAsync(&terms, need, st));   // one allocation for the whole call
-        const int rc = pack_device<F>(pl, glwe_out, lwe_in, pksk_ntt, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, (W *)terms, st);
-        if (!workspace && terms) (void)hipFreeAsync(terms, st);
-        return rc;
-    }
-    Staging s(st);
+    Staging s(where, st);
     typename F::KeyStore ks;
     const typename F::Key dkey = lwe_dim_in ? F::key_in(pl, s, pksk_ntt, kb, ks) : typename F::Key{};
     const W *din = (const W *)s.in(lwe_in, ib);
-    W *dout = (W *)s.out(glwe_out, ob), *dterms = (W *)s.alloc(need);
+    W *dout = (W *)s.out(glwe_out, ob), *dterms = (W *)s.workspace(workspace, need, lwe_dim_in != 0);   // one block for the whole call
     if (int rc = s.status()) return rc;
     if (int rc = pack_device<F>(pl, dout, din, dkey, lwe_dim_in, lwe_count, glwe_dim, base_log, levels, batch, dterms, st)) return rc;
     return s.finish();

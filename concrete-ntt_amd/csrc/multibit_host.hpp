@@ -1,6 +1,7 @@
 // The host side of the multi-bit blind rotation and bootstrap, once for the native plans (include/cntt_multibit.h, host_native_ext.hip
 // through host_native_multibit.inc) and the prime plans (include/cntt_prime_multibit.h, host_prime.hip through host_prime_multibit.inc):
-// argument checks, the host-slice staging, the workspace layout and the loop over the groups.  Internal, never installed.  Templates over
+// argument checks, the workspace layout and the loop over the groups, each call on one path for device pointers and host slices
+// through Staging (host_common.hpp).  Internal, never installed.  Templates over
 // a family F as in pbs_host.hpp, which this file builds on: the bootstrap family plus the multibit_* members NativePbs
 // (host_native_ext.hip) and PrimePbs<T> (host_prime_pbs.inc) show.  The stand-alone *_multibit_accumulate_batch calls stay with their
 // families (residue planes on one side, plain buffers on the other) and share the grouping check only.
@@ -123,22 +124,15 @@ int multibit_blind_rotate(const typename F::Plan *pl, typename F::Word *acc, con
     const size_t kb = multibit_key_bytes<F>(pl, lwe_dim, glwe_dim, levels, grouping);
     Operand ops[MULTIBIT_MAX_OPERANDS] = {{"acc", acc, Z.acc, w, true}, {"lut", lut, lb, w, false}, {"rot_t", rot_t, Z.rot, sizeof(uint32_t), false}};
     if (int rc = multibit_operands<F>(pl, ops, bsk, kb, workspace, workspace_bytes)) return rc;
-    if (where == CNTT_MEM_DEVICE) {
-        void *ws = workspace;
-        if (!ws && lwe_dim) HIP_TRY(hipMallocAsync(&ws, Z.rotate(), st));   // one allocation for the whole loop
-        const int rc = multibit_rotate_device<F>(pl, acc, lut, lut_per_element != 0, rot_t, bsk, lwe_dim, glwe_dim, base_log, levels, grouping,
-                                                 batch, Z, static_cast<char *>(ws), st);
-        if (!workspace && ws) (void)hipFreeAsync(ws, st);
-        return rc;
-    }
-    if (int rc = check_rot_host(pl->n, rot_t, (lwe_dim + 1) * batch, "rot_t")) return rc;
-    Staging s(st);
+    Staging s(where, st);
+    if (s.host())
+        if (int rc = check_rot_host(pl->n, rot_t, (lwe_dim + 1) * batch, "rot_t")) return rc;
     typename F::KeyStore ks;
     const typename F::Key dkey = lwe_dim ? F::key_in(pl, s, bsk, kb, ks) : typename F::Key{};
     const W *dlut = (const W *)s.in(lut, lb);
     const uint32_t *drot = (const uint32_t *)s.in(rot_t, Z.rot);
     W *dacc = (W *)s.out(acc, Z.acc);
-    char *dws = (char *)s.alloc(Z.rotate());
+    char *dws = (char *)s.workspace(workspace, Z.rotate(), lwe_dim != 0);   // one block for the whole loop
     if (int rc = s.status()) return rc;
     if (int rc = multibit_rotate_device<F>(pl, dacc, dlut, lut_per_element != 0, drot, dkey, lwe_dim, glwe_dim, base_log, levels, grouping,
                                            batch, Z, dws, st))
@@ -181,20 +175,12 @@ int multibit_bootstrap(const typename F::Plan *pl, typename F::Word *lwe_out, co
     Operand ops[MULTIBIT_MAX_OPERANDS] = {{"lwe_out", lwe_out, ob, w, true}, {"lwe_in", lwe_in, ib, w, false}, {"lut", lut, lb, w, false}};
     if (int rc = multibit_operands<F>(pl, ops, bsk, kb, workspace, workspace_bytes)) return rc;
     if (F::logn(pl) > F::MODSWITCH_MAX_LOGN) return fail(CNTT_EINVAL, "ntt_size too large for the modulus switch");
-    if (where == CNTT_MEM_DEVICE) {
-        void *ws = workspace;
-        if (!ws) HIP_TRY(hipMallocAsync(&ws, Z.total(), st));   // one allocation for the whole call
-        const int rc = multibit_bootstrap_device<F>(pl, lwe_out, lwe_in, lut, lut_per_element != 0, bsk, lwe_dim, glwe_dim, base_log, levels,
-                                                    grouping, batch, Z, static_cast<char *>(ws), st);
-        if (!workspace) (void)hipFreeAsync(ws, st);
-        return rc;
-    }
-    Staging s(st);
+    Staging s(where, st);
     typename F::KeyStore ks;
     const typename F::Key dkey = lwe_dim ? F::key_in(pl, s, bsk, kb, ks) : typename F::Key{};
     const W *din = (const W *)s.in(lwe_in, ib), *dlut = (const W *)s.in(lut, lb);
     W *dout = (W *)s.out(lwe_out, ob);
-    char *dws = (char *)s.alloc(Z.total());
+    char *dws = (char *)s.workspace(workspace, Z.total());   // one block for the whole call
     if (int rc = s.status()) return rc;
     if (int rc = multibit_bootstrap_device<F>(pl, dout, din, dlut, lut_per_element != 0, dkey, lwe_dim, glwe_dim, base_log, levels, grouping,
                                               batch, Z, dws, st))

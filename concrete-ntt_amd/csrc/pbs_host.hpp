@@ -1,5 +1,7 @@
 // The host side of the programmable bootstrap, once for the native plans (include/cntt_pbs.h, host_native_ext.hip) and the prime plans
-// (include/cntt_prime_pbs.h, host_prime.hip): argument checks, the host-slice staging, the workspace layout and the blind rotation loop.
+// (include/cntt_prime_pbs.h, host_prime.hip): argument checks, the workspace layout and the blind rotation loop.  Every call is one
+// path for device pointers and host slices: after its checks it takes its operands and its workspace from a Staging(where, stream)
+// (host_common.hpp) and runs its _device function on them; only check_rot_host asks which of the two it is.
 // Internal, never installed.  Every function here is a template over a family F, one struct of static members per plan family that supplies
 // what the two differ in and nothing else: NativePbs (host_native_ext.hip) and PrimePbs<T> (host_prime_pbs.inc) show the members.
 // lwe_host.hpp, on top of this file, does the same for the keyswitch, the keyswitch + bootstrap call and the packing keyswitch, and
@@ -44,11 +46,10 @@ int gadget_decompose(const typename F::Plan *pl, typename F::Word *terms, const 
     if (!terms || !polys) return fail(CNTT_EINVAL, "NULL argument");
     const size_t pb = batch * npolys * pl->n * F::word(pl), tb = pb * levels;
     if (ranges_overlap(terms, tb, polys, pb)) return fail(CNTT_EINVAL, "terms overlaps polys");
-    if (where == CNTT_MEM_DEVICE) return F::gadget(pl, terms, polys, rot, npolys, base_log, levels, mode, batch, st);
     const bool rotated = mode != CNTT_SRC_PLAIN;
-    if (rotated)
+    Staging s(where, st);
+    if (s.host() && rotated)
         if (int rc = check_rot_host(pl->n, rot, batch, "rot")) return rc;
-    Staging s(st);
     W *dt = (W *)s.out(terms, tb);
     const W *dp = (const W *)s.in(polys, pb);
     const uint32_t *dr = rotated ? (const uint32_t *)s.in(rot, batch * sizeof(uint32_t)) : nullptr;
@@ -114,8 +115,7 @@ int lwe_modswitch(const typename F::Plan *pl, uint32_t *rot_t, const typename F:
     if (!lwe) return fail(CNTT_EINVAL, "lwe is NULL");
     const size_t rb = (lwe_dim + 1) * batch * sizeof(uint32_t), lb = (lwe_dim + 1) * batch * F::word(pl);
     if (ranges_overlap(rot_t, rb, lwe, lb)) return fail(CNTT_EINVAL, "rot_t overlaps lwe");
-    if (where == CNTT_MEM_DEVICE) return modswitch_device<F>(pl, rot_t, lwe, lwe_dim, batch, st);
-    Staging s(st);
+    Staging s(where, st);
     uint32_t *dr = (uint32_t *)s.out(rot_t, rb);
     const typename F::Word *dl = (const typename F::Word *)s.in(lwe, lb);
     if (int rc = s.status()) return rc;
@@ -134,8 +134,7 @@ int sample_extract(const typename F::Plan *pl, typename F::Word *lwe_out, const 
     if (!glwe) return fail(CNTT_EINVAL, "glwe is NULL");
     const size_t w = F::word(pl), ob = batch * (glwe_dim * pl->n + 1) * w, gb = batch * (glwe_dim + 1) * pl->n * w;
     if (ranges_overlap(lwe_out, ob, glwe, gb)) return fail(CNTT_EINVAL, "lwe_out overlaps glwe");
-    if (where == CNTT_MEM_DEVICE) return extract_device<F>(pl, lwe_out, glwe, glwe_dim, index, batch, st);
-    Staging s(st);
+    Staging s(where, st);
     W *dout = (W *)s.out(lwe_out, ob);
     const W *dg = (const W *)s.in(glwe, gb);
     if (int rc = s.status()) return rc;
@@ -175,22 +174,15 @@ int blind_rotate(const typename F::Plan *pl, typename F::Word *acc, const typena
     if (ranges_overlap(acc, Z.acc, lut, lb)) return fail(CNTT_EINVAL, "acc overlaps lut");
     if (ranges_overlap(acc, Z.acc, rot_t, Z.rot)) return fail(CNTT_EINVAL, "acc overlaps rot_t");
     if (workspace && ranges_overlap(acc, Z.acc, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "acc overlaps workspace");
-    if (where == CNTT_MEM_DEVICE) {
-        void *digits = workspace;
-        if (!digits && lwe_dim) HIP_TRY(hipMallocAsync(&digits, Z.digits, st));   // one allocation for the whole loop
-        const int rc = blind_rotate_device<F>(pl, acc, lut, lut_per_element != 0, rot_t, bsk, lwe_dim, glwe_dim, base_log, levels, batch,
-                                              (W *)digits, st);
-        if (!workspace && digits) (void)hipFreeAsync(digits, st);
-        return rc;
-    }
-    if (int rc = check_rot_host(pl->n, rot_t, (lwe_dim + 1) * batch, "rot_t")) return rc;
+    Staging s(where, st);
+    if (s.host())
+        if (int rc = check_rot_host(pl->n, rot_t, (lwe_dim + 1) * batch, "rot_t")) return rc;
     const size_t kb = F::key_bytes(pl, lwe_dim * (glwe_dim + 1) * levels * (glwe_dim + 1));
-    Staging s(st);
     typename F::KeyStore ks;
     const typename F::Key dkey = lwe_dim ? F::key_in(pl, s, bsk, kb, ks) : typename F::Key{};
     const W *dlut = (const W *)s.in(lut, lb);
     const uint32_t *drot = (const uint32_t *)s.in(rot_t, Z.rot);
-    W *dacc = (W *)s.out(acc, Z.acc), *ddig = (W *)s.alloc(Z.digits);
+    W *dacc = (W *)s.out(acc, Z.acc), *ddig = (W *)s.workspace(workspace, Z.digits, lwe_dim != 0);   // one block for the whole loop
     if (int rc = s.status()) return rc;
     if (int rc = blind_rotate_device<F>(pl, dacc, dlut, lut_per_element != 0, drot, dkey, lwe_dim, glwe_dim, base_log, levels, batch, ddig, st))
         return rc;
@@ -233,21 +225,13 @@ int bootstrap(const typename F::Plan *pl, typename F::Word *lwe_out, const typen
         if (ranges_overlap(lwe_in, ib, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lwe_in overlaps workspace");
         if (ranges_overlap(lut, lb, workspace, workspace_bytes)) return fail(CNTT_EINVAL, "lut overlaps workspace");
     }
-    if (where == CNTT_MEM_DEVICE) {
-        void *ws = workspace;
-        if (!ws) HIP_TRY(hipMallocAsync(&ws, Z.total(), st));   // one allocation for the whole call
-        const int rc = bootstrap_device<F>(pl, lwe_out, lwe_in, lut, lut_per_element != 0, bsk, lwe_dim, glwe_dim, base_log, levels, batch, Z,
-                                           static_cast<char *>(ws), st);
-        if (!workspace) (void)hipFreeAsync(ws, st);
-        return rc;
-    }
     const size_t kb = F::key_bytes(pl, lwe_dim * (glwe_dim + 1) * levels * (glwe_dim + 1));
-    Staging s(st);
+    Staging s(where, st);
     typename F::KeyStore ks;
     const typename F::Key dkey = lwe_dim ? F::key_in(pl, s, bsk, kb, ks) : typename F::Key{};
     const W *din = (const W *)s.in(lwe_in, ib), *dlut = (const W *)s.in(lut, lb);
     W *dout = (W *)s.out(lwe_out, ob);
-    char *dws = (char *)s.alloc(Z.total());
+    char *dws = (char *)s.workspace(workspace, Z.total());   // one block for the whole call
     if (int rc = s.status()) return rc;
     if (int rc = bootstrap_device<F>(pl, dout, din, dlut, lut_per_element != 0, dkey, lwe_dim, glwe_dim, base_log, levels, batch, Z, dws, st))
         return rc;

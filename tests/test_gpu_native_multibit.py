@@ -141,7 +141,9 @@ def composed_rotate(torch, plan, lut, rot_t, kp, L, k, beta, ell, g, batch):
     return acc
 
 
-def rotation_case(torch, kind, n, k, g, L, batch, beta, ell, tag):
+def rotation_case(torch, kind, n, k, g, L, batch, beta, ell, tag, where="device", with_ws=False):
+    """where = "host": the call on host slices (a host-side workspace is checked and then ignored); with_ws: the figure of
+    multibit_pbs_workspace_bytes, which covers what the rotation alone needs"""
     plan = KINDS[kind].try_new(n)
     J = (k + 1) * ell
     rng = np.random.default_rng(seed("nmb/rot", kind, n, k, g, L, tag))
@@ -152,8 +154,15 @@ def rotation_case(torch, kind, n, k, g, L, batch, beta, ell, tag):
     key_words = random_key_words(rng, plan, ((L // g) * J * (k + 1)) << g)
     # (no mask words: no key, and nothing for fwd_batch to transform)
     kp = key_planes(torch, plan, key_words) if L else [torch.zeros(0, dtype=torch.int32, device="cuda") for _ in range(plan.NPRIMES)]
+    nws = plan.multibit_pbs_workspace_bytes(L, k, ell, g, batch)
+    if where == "host":
+        h_acc = to_array(plan, [1] * (batch * (k + 1) * n))
+        plan.multibit_blind_rotate_batch(h_acc, lut, rot_t, [host(x, np.uint32).copy() for x in kp], L, k, beta, ell, g,
+                                         workspace=np.zeros(nws, dtype=np.uint8) if with_ws else None)
+        return plan, lut, rot_t, key_words, kp, to_ints(plan, h_acc)
     acc = dev(torch, to_array(plan, [1] * (batch * (k + 1) * n)))
-    plan.multibit_blind_rotate_batch(acc, dev(torch, lut), dev(torch, rot_t), kp, L, k, beta, ell, g)
+    ws = torch.zeros(nws, dtype=torch.uint8, device="cuda") if with_ws else None
+    plan.multibit_blind_rotate_batch(acc, dev(torch, lut), dev(torch, rot_t), kp, L, k, beta, ell, g, workspace=ws)
     torch.cuda.synchronize()
     return plan, lut, rot_t, key_words, kp, to_ints(plan, host(acc, plan.word_dtype))
 
@@ -178,6 +187,12 @@ def test_blind_rotate_at_4096_and_without_mask_words():
     assert got == composed_rotate(torch, plan, lut, rot_t, kp, 2, 1, 15, 2, 2, 1)
     plan, lut, rot_t, _, kp, got = rotation_case(torch, "native32_plan32", 32, 1, 3, 0, 2, 7, 2, "zero")
     assert got == composed_rotate(torch, plan, lut, rot_t, kp, 0, 1, 7, 2, 3, 2)
+    # one group and no group, with a caller workspace on the device and through the host path with and without one: the same words
+    for L in (2, 0):
+        plan, lut, rot_t, _, kp, got = rotation_case(torch, "native32_plan32", 32, 1, 2, L, 2, 7, 2, "frames")
+        assert got == composed_rotate(torch, plan, lut, rot_t, kp, L, 1, 7, 2, 2, 2), L
+        for where, with_ws in (("device", True), ("host", False), ("host", True)):
+            assert rotation_case(torch, "native32_plan32", 32, 1, 2, L, 2, 7, 2, "frames", where, with_ws)[5] == got, (L, where, with_ws)
 
 
 # -- 3. the bootstrap ---------------------------------------------------------------------------------------------------------------------
@@ -234,6 +249,24 @@ def test_bootstrap_equals_its_three_steps(kind, g):
     graph.replay()
     torch.cuda.synchronize()
     assert np.array_equal(host(out3, plan.word_dtype), want)
+
+
+def test_bootstrap_without_mask_words_equals_its_three_steps():
+    """lwe_dim = 0: no group, no key; device without and with a caller workspace, and the host path"""
+    torch = _torch()
+    kind, n, k, g, L, batch, ell, beta = "native32_plan32", 64, 1, 2, 0, 2, 2, 8
+    plan, lut, lwe, _ = bootstrap_case(torch, kind, n, k, g, L, batch, ell, "zero")
+    kp = [torch.zeros(0, dtype=torch.int32, device="cuda") for _ in range(plan.NPRIMES)]
+    want = three_steps(torch, plan, lut, lwe, kp, L, k, beta, ell, g, batch)
+    assert want.any()
+    for ws in (None, torch.zeros(plan.multibit_pbs_workspace_bytes(L, k, ell, g, batch), dtype=torch.uint8, device="cuda")):
+        out = dev(torch, to_array(plan, [1] * (batch * (k * n + 1))))
+        plan.multibit_bootstrap_batch(out, dev(torch, lwe), dev(torch, lut), kp, L, k, beta, ell, g, workspace=ws)
+        torch.cuda.synchronize()
+        assert np.array_equal(host(out, plan.word_dtype), want), ws is None
+    hout = to_array(plan, [3] * (batch * (k * n + 1)))
+    plan.multibit_bootstrap_batch(hout, lwe, lut, [host(x, np.uint32) for x in kp], L, k, beta, ell, g)
+    assert np.array_equal(hout, want)
 
 
 def test_device_refusals_leave_the_outputs_untouched():

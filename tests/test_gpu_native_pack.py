@@ -185,6 +185,8 @@ def test_pack_matches_model(w, where):
         got = run_pack(torch, plan, where, lwe, key, lin, m, k, beta, ell, batch)
         assert got == want, (w, where, n, batch, m, lin, k, beta, ell, "first bad word", first_difference(got, want))
         if lin == 0:                                            # the poison is gone: zero masks, zero tail of the body polynomial
+            # (no chunk, no key: a workspace the caller brings is not touched, and without one the device path allocates none)
+            assert run_pack(torch, plan, where, lwe, key, lin, m, k, beta, ell, batch, with_ws=True) == want, (w, where, "lin = 0 with a workspace")
             for g in range(batch):
                 o = got[g * (k + 1) * n:(g + 1) * (k + 1) * n]
                 assert not any(o[:k * n]) and not any(o[k * n + m:]) and o[k * n:k * n + m] == [lwe[(g * m + t) * (lin + 1) + lin] for t in range(m)]

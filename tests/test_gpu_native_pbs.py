@@ -149,7 +149,8 @@ def random_key_words(rng, plan, npoly):
 def key_planes(torch, plan, key_words):
     res_t = torch.int64 if plan.RES == 8 else torch.int32
     kr = [torch.empty(len(key_words) // per(plan) * plan.ntt_size(), dtype=res_t, device="cuda") for _ in range(plan.NPRIMES)]
-    plan.fwd_batch(dev(torch, key_words), kr, binary=plan.BINARY)
+    if len(key_words):   # (no key at all: lwe_dim = 0)
+        plan.fwd_batch(dev(torch, key_words), kr, binary=plan.BINARY)
     return kr
 
 
@@ -253,7 +254,8 @@ def per_iteration_references(torch, plan, lut_t, per_element, rot_t, kr, L, k, b
     return acc, pp[0]
 
 
-def check_blind_rotate(torch, kind, n, k, per_element, with_ws, L=5, beta=6):
+def check_blind_rotate(torch, kind, n, k, per_element, with_ws, L=5, beta=6, where="device"):
+    """where = "host": the call on host slices (a host-side workspace is checked and then ignored), the references on the device"""
     plan = KINDS[kind].try_new(n)
     assert plan is not None
     ell = min(3, plan.max_terms() // (k + 1))
@@ -264,12 +266,19 @@ def check_blind_rotate(torch, kind, n, k, per_element, with_ws, L=5, beta=6):
     rot_t = dev(torch, rot_rows(rng, n, L, batch))
     kr = key_planes(torch, plan, random_key_words(rng, plan, L * (k + 1) * ell * (k + 1)))
     acc = dev(torch, random_words(rng, plan, batch * (k + 1) * n))   # written only: the prior content must not matter
-    ws = workspace(torch, plan, L, k, ell, batch) if with_ws else None
-    plan.blind_rotate_batch(acc, lut_t, rot_t, kr, L, k, beta, ell, workspace=ws, lut_per_element=per_element)
+    if where == "host":
+        acc_h = host(acc, plan.word_dtype).copy()
+        ws = np.zeros(plan.pbs_workspace_bytes(L, k, ell, batch), dtype=np.uint8) if with_ws else None
+        plan.blind_rotate_batch(acc_h, host(lut_t, plan.word_dtype).copy(), host(rot_t, np.uint32).copy(),
+                                [host(p, plan.res_dtype).copy() for p in kr], L, k, beta, ell, workspace=ws, lut_per_element=per_element)
+        acc = dev(torch, acc_h)
+    else:
+        ws = workspace(torch, plan, L, k, ell, batch) if with_ws else None
+        plan.blind_rotate_batch(acc, lut_t, rot_t, kr, L, k, beta, ell, workspace=ws, lut_per_element=per_element)
     torch.cuda.synchronize()
     inplace, pingpong = per_iteration_references(torch, plan, lut_t, per_element, rot_t, kr, L, k, beta, ell, batch)
     assert torch.equal(inplace, pingpong), (kind, n, k, "the two per-iteration references differ")
-    assert torch.equal(acc, inplace), (kind, n, k, per_element, with_ws, "blind_rotate_batch differs from the per-iteration calls")
+    assert torch.equal(acc, inplace), (kind, n, k, per_element, with_ws, L, where, "blind_rotate_batch differs from the per-iteration calls")
 
 
 @pytest.mark.parametrize("kind", sorted(KINDS))
@@ -277,6 +286,11 @@ def test_blind_rotate_equals_per_iteration_calls_n256(kind):
     torch = _torch()
     for k, per_element, with_ws in ((1, False, False), (1, True, True), (2, False, True), (2, True, False)):
         check_blind_rotate(torch, kind, 256, k, per_element, with_ws)
+    # the host path with and without a workspace, and on all three paths lwe_dim = 0: the set-up alone, no digits, no key, and a
+    # workspace the call does not touch (the device path allocates none)
+    for per_element, with_ws, L, where in ((False, True, 2, "host"), (True, False, 2, "host"), (False, True, 0, "device"),
+                                           (True, False, 0, "device"), (False, False, 0, "host")):
+        check_blind_rotate(torch, kind, 256, 1, per_element, with_ws, L=L, where=where)
 
 
 @pytest.mark.parametrize("n", [1024, 4096])
@@ -369,9 +383,19 @@ def test_blind_rotate_matches_model_and_oracle(oracle, kind):
                                                   ("native128_plan32", 256, "device", True), ("native_binary32_plan52", 256, "device", False),
                                                   ("native32_plan32", 256, "host", False), ("native64_plan32", 1024, "host", True)])
 def test_bootstrap_equals_its_three_steps(kind, n, where, with_ws):
+    check_bootstrap_steps(kind, n, where, with_ws, L=4, batch=5)
+
+
+@pytest.mark.parametrize("where,with_ws", [("device", True), ("device", False), ("host", True)])
+def test_bootstrap_without_mask_words_equals_its_three_steps(where, with_ws):
+    """lwe_dim = 0: the body alone -- no iteration, no key, and of the workspace only rot_t and the accumulator"""
+    check_bootstrap_steps("native64_plan32", 256, where, with_ws, L=0, batch=2)
+
+
+def check_bootstrap_steps(kind, n, where, with_ws, L, batch):
     torch = _torch()
     plan = KINDS[kind].try_new(n)
-    L, k, beta, batch = 4, 1, 7, 5
+    k, beta = 1, 7
     ell = min(3, plan.max_terms() // (k + 1))
     rng = np.random.default_rng(seed(kind, n, where))
     lwe_a = random_words(rng, plan, batch * (L + 1))
@@ -399,6 +423,13 @@ def test_bootstrap_equals_its_three_steps(kind, n, where, with_ws):
         torch.cuda.synchronize()
     assert np.array_equal(fro(one, plan.word_dtype), fro(steps, plan.word_dtype)), (kind, n, where, with_ws)
     assert fro(one, plan.word_dtype).any()
+    if L == 0:   # and the model: coefficient 0 of X^(-ms(body)) lut
+        w, logn, lut_i, lwe_i = wbits(plan), n.bit_length() - 1, to_ints(plan, lut_a), to_ints(plan, lwe_a)
+        want = []
+        for b in range(batch):
+            a = (2 * n - ms(lwe_i[b], w, logn)) % (2 * n)
+            want += model_extract([source(lut_i[q * n:(q + 1) * n], a, w, "rotate") for q in range(k + 1)], 0, w)
+        assert to_ints(plan, fro(one, plan.word_dtype)) == want, (kind, where, with_ws, "lwe_dim = 0 against the model")
 
 
 # -- 6. the bootstrap bootstraps ------------------------------------------------------------------------------------------------------------

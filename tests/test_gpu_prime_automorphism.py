@@ -218,16 +218,17 @@ def test_autoks_at_larger_sizes(p, n, k, batch):
 @pytest.mark.parametrize("with_ws", [False, True])
 def test_autoks_on_the_host_path(p, with_ws):
     torch = _torch()
-    n, k, beta, ell, batch = 64, 1, 6, 3, 3
+    n, beta, ell, batch = 64, 6, 3, 3
     plan = make_plan(p, n)
     rng = np.random.default_rng(seed("autoks-host", p))
-    kw, kt = key_for(torch, plan, p, rng, k, ell, n)
-    ct = words_with_zeros(rng, p, batch * (k + 1) * n)
-    for t, add in ((n + 1, True), (5, False)):
-        got = run_autoks(torch, plan, p, "host", ct, kt, t, k, beta, ell, add, batch, with_ws)
-        want = run_autoks(torch, plan, p, "device", ct, kt, t, k, beta, ell, add, batch)
-        assert np.array_equal(got, want), (p, t, add, first_difference(got, want))
-        assert np.array_equal(got, np.array(model_autoks_batch(ct.tolist(), kw.tolist(), p, t, k, n, beta, ell, add, batch), dtype=dt(p)))
+    for k in (1, 0):   # glwe_dim = 0: no digits, no key, nothing of the workspace
+        kw, kt = key_for(torch, plan, p, rng, k, ell, n)
+        ct = words_with_zeros(rng, p, batch * (k + 1) * n)
+        for t, add in ((n + 1, True), (5, False)):
+            got = run_autoks(torch, plan, p, "host", ct, kt, t, k, beta, ell, add, batch, with_ws)
+            want = run_autoks(torch, plan, p, "device", ct, kt, t, k, beta, ell, add, batch)
+            assert np.array_equal(got, want), (p, k, t, add, first_difference(got, want))
+            assert np.array_equal(got, np.array(model_autoks_batch(ct.tolist(), kw.tolist(), p, t, k, n, beta, ell, add, batch), dtype=dt(p)))
 
 
 # -- 4. the trace --------------------------------------------------------------------------------------------------------------------------
@@ -272,6 +273,12 @@ def test_trace_equals_steps_calls_of_the_keyswitch(p, n, k):
         assert np.array_equal(got, want), (p, n, k, steps, first_difference(got, want))
         if steps == 0:
             assert np.array_equal(got, ct)
+        if steps <= 2 and n <= 64:
+            # no step (a copy), one step (the digits alone, and with glwe_dim = 0 nothing of the workspace) and two (the second
+            # ciphertext too): the other workspace setting on the device, and the host path with and without a workspace
+            for where, with_ws in (("device", steps % 2 == 0), ("host", False), ("host", True)):
+                again = run_trace(torch, plan, p, where, ct, keys, steps, k, beta, ell, batch, with_ws=with_ws)
+                assert np.array_equal(again, want), (p, n, k, steps, where, with_ws, first_difference(again, want))
     if n <= 64:
         assert np.array_equal(run_trace(torch, plan, p, "host", ct, kt, logn, k, beta, ell, batch, with_ws=True), got)
 

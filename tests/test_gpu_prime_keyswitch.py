@@ -198,6 +198,12 @@ def test_combined_call_equals_the_two_calls_and_chains(p, n):
         torch.cuda.synchronize()
         assert torch.equal(one, rounds[0]) and torch.equal(two, rounds[1]), (p, n, w is None)
     assert rounds[0].any() and rounds[1].any()
+    if n == 64:                                     # the host path, with a host-side workspace (checked, then ignored) and without
+        h = {name: host(t, dt(p)).copy() for name, t in a.items()}
+        for w in (None, np.zeros(plan.ks_pbs_workspace_bytes(L, k, ell, batch), dtype=np.uint8)):
+            one = np.zeros(batch * (big + 1), dtype=dt(p))
+            plan.keyswitch_bootstrap_batch(one, h["lwe"], h["ksk"], ks_beta, ks_ell, h["lut"], h["bsk"], L, k, beta, ell, workspace=w, row_stride=stride)
+            assert np.array_equal(one, host(rounds[0], dt(p))), (p, n, "host", w is None)
 
 
 def test_graph_capture_of_the_combined_call_with_a_caller_workspace():

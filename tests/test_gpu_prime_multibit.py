@@ -166,6 +166,24 @@ def test_blind_rotate_equals_the_public_calls_and_the_model(p, n, g, k):
         if n <= 32 or (g <= 2 and k == 1):
             want = model_multibit_rotate(lut.tolist(), rot.tolist(), key.tolist(), p, n, L, k, beta, ell, g, batch, per_element)
             assert [int(x) for x in got] == want, (p, n, g, k, beta, ell)
+        if si == 0 and (g, k) == (2, 1):
+            # the same words with a caller workspace on the device and through the host path with and without one; then no group at
+            # all (lwe_dim = 0: the set-up alone, a workspace the call does not touch) on the same three paths and without one
+            for Lf, want_t in ((L, acc), (0, composition(torch, plan, p, n, lut_t, rot_t[L * batch:], bsk, 0, k, beta, ell, g, batch))):
+                rot_f, nws = rot_t[(L - Lf) * batch:], plan.multibit_pbs_workspace_bytes(Lf, k, ell, g, batch)
+                key_f = bsk if Lf else bsk[:0]
+                for where, with_ws in (("device", False), ("device", True), ("host", False), ("host", True)):
+                    if where == "host":
+                        out = np.zeros(batch * (k + 1) * n, dtype=dt(p))
+                        plan.multibit_blind_rotate_batch(out, lut, host(rot_f, np.uint32).copy(), host(key_f, dt(p)).copy(), Lf, k, beta, ell, g,
+                                                         workspace=np.zeros(nws, dtype=np.uint8) if with_ws else None, lut_per_element=per_element)
+                    else:
+                        out_t = zeros(torch, p, batch * (k + 1) * n)
+                        ws = torch.zeros(nws, dtype=torch.uint8, device="cuda") if with_ws else None
+                        plan.multibit_blind_rotate_batch(out_t, lut_t, rot_f, key_f, Lf, k, beta, ell, g, workspace=ws, lut_per_element=per_element)
+                        torch.cuda.synchronize()
+                        out = host(out_t, dt(p))
+                    assert np.array_equal(out, host(want_t, dt(p))), (p, n, Lf, where, with_ws)
 
 
 def test_blind_rotate_past_a_wavefront_resident_transform():
@@ -201,9 +219,19 @@ def test_blind_rotate_past_a_wavefront_resident_transform():
 @pytest.mark.parametrize("p,n,where,with_ws", [(P62, 1024, "device", True), (P62, 1024, "device", False), (PM64, 64, "host", True),
                                                (P30, 64, "host", False), (P32, 2048, "device", True)])
 def test_bootstrap_equals_its_three_steps(p, n, where, with_ws):
+    check_bootstrap_steps(p, n, where, with_ws, L=6, batch=5)
+
+
+@pytest.mark.parametrize("p,where,with_ws", [(P62, "device", True), (P62, "device", False), (P30, "host", True)])
+def test_bootstrap_without_mask_words_equals_its_three_steps(p, where, with_ws):
+    """lwe_dim = 0: no group, no key, and of the workspace only rot_t and the accumulator"""
+    check_bootstrap_steps(p, 64, where, with_ws, L=0, batch=2)
+
+
+def check_bootstrap_steps(p, n, where, with_ws, L, batch):
     torch = _torch()
     plan = make_plan(p, n)
-    L, k, beta, ell, g, batch = 6, 1, 7, 3, 3 if n == 64 else 2, 5
+    k, beta, ell, g = 1, 7, 3, 3 if n == 64 else 2
     rng = np.random.default_rng(seed("mbboot", p, n, where))
     lwe_a = random_words(rng, p, batch * (L + 1))
     lut_a = random_words(rng, p, (k + 1) * n)

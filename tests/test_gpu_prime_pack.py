@@ -113,6 +113,9 @@ def test_pack_matches_model(p, where):
         got = run_pack(torch, plans[n], p, where, lwe, key, lin, m, k, beta, ell, batch)
         assert np.array_equal(got, want), (p, where, n, batch, m, lin, k, beta, ell, "first bad word", first_difference(got, want))
         if lin == 0:                                            # the poison is gone: zero masks, zero tail of the body polynomial
+            # (no chunk, no key: a workspace the caller brings is not touched, and without one the device path allocates none)
+            again = run_pack(torch, plans[n], p, where, lwe, key, lin, m, k, beta, ell, batch, with_ws=True)
+            assert np.array_equal(again, want), (p, where, "lin = 0 with a workspace")
             o = got.reshape(batch, k + 1, n)
             assert not o[:, :k].any() and not o[:, k, m:].any() and np.array_equal(o[:, k, :m], lwe.reshape(batch, m))
 

@@ -327,22 +327,33 @@ def per_iteration_reference(torch, plan, p, lut_t, per_element, rot_t, bsk, L, k
     return acc
 
 
-def check_blind_rotate(torch, p, n, k, L, batch, per_element, with_ws, beta=7, ell=3):
+def check_blind_rotate(torch, p, n, k, L, batch, per_element, with_ws, beta=7, ell=3, where="device"):
+    """where = "host": the call on host slices (a host-side workspace is checked and then ignored), the reference on the device"""
     plan = make_plan(p, n)
     rng = np.random.default_rng(seed("br", p, n, k, L, batch, per_element, with_ws))
     lut_t = dev(torch, random_words(rng, p, (batch if per_element else 1) * (k + 1) * n))
     rot_t = dev(torch, rot_rows(rng, n, L, batch))
     bsk = dev(torch, random_words(rng, p, L * (k + 1) * ell * (k + 1) * n))      # any canonical words do for this comparison
     acc = dev(torch, random_words(rng, p, batch * (k + 1) * n))                  # written only: the prior content must not matter
-    ws = workspace(torch, plan, L, k, ell, batch) if with_ws else None
-    plan.blind_rotate_batch(acc, lut_t, rot_t, bsk, L, k, beta, ell, workspace=ws, lut_per_element=per_element)
+    if where == "host":
+        acc_h = host(acc, dt(p)).copy()
+        ws = np.zeros(plan.pbs_workspace_bytes(L, k, ell, batch), dtype=np.uint8) if with_ws else None
+        plan.blind_rotate_batch(acc_h, host(lut_t, dt(p)).copy(), host(rot_t, np.uint32).copy(), host(bsk, dt(p)).copy(), L, k, beta, ell,
+                                workspace=ws, lut_per_element=per_element)
+        acc = dev(torch, acc_h)
+    else:
+        ws = workspace(torch, plan, L, k, ell, batch) if with_ws else None
+        plan.blind_rotate_batch(acc, lut_t, rot_t, bsk, L, k, beta, ell, workspace=ws, lut_per_element=per_element)
     torch.cuda.synchronize()
     want = per_iteration_reference(torch, plan, p, lut_t, per_element, rot_t, bsk, L, k, beta, ell, batch)
-    assert torch.equal(acc, want), (p, n, k, L, batch, per_element, with_ws, "blind_rotate_batch differs from the per-iteration calls")
+    assert torch.equal(acc, want), (p, n, k, L, batch, per_element, with_ws, where, "blind_rotate_batch differs from the per-iteration calls")
     assert L == 0 or bool(acc.any())
 
 
 COVER = [(0, 1, False, False), (1, 3, True, True), (5, 3, False, True), (5, 1, True, False)]      # (L, batch, per-element lut, workspace)
+# the host path with and without a workspace, and lwe_dim = 0 (the set-up alone: no digits, no key, a workspace the call does not
+# touch) on the two paths COVER leaves out: (L, batch, per-element lut, workspace, where)
+COVER_FRAMES = [(2, 2, False, True, "host"), (2, 2, True, False, "host"), (0, 2, False, True, "device"), (0, 2, True, False, "host")]
 
 
 @pytest.mark.parametrize("n,k", [(1024, 1), (1024, 2), (64, 1), (64, 2), (4096, 1), (1024, 4), (64, 4)])
@@ -352,6 +363,9 @@ def test_blind_rotate_equals_per_iteration_calls(p, n, k):
     torch = _torch()
     for L, batch, per_element, with_ws in COVER:
         check_blind_rotate(torch, p, n, k, L, batch, per_element, with_ws)
+    if (n, k) == (64, 1):
+        for L, batch, per_element, with_ws, where in COVER_FRAMES:
+            check_blind_rotate(torch, p, n, k, L, batch, per_element, with_ws, where=where)
 
 
 @pytest.mark.parametrize("p", [P30, P32])
@@ -403,9 +417,19 @@ def test_blind_rotate_matches_big_integer_model(p, n):
                                                (P63, 4096, "device", False), (P30, 1024, "host", False), (PM64, 1024, "host", True),
                                                (P32, 64, "device", True)])
 def test_bootstrap_equals_its_three_steps(p, n, where, with_ws):
+    check_bootstrap_steps(p, n, where, with_ws, L=4, batch=5)
+
+
+@pytest.mark.parametrize("p,where,with_ws", [(P62, "device", True), (P62, "device", False), (P30, "host", True)])
+def test_bootstrap_without_mask_words_equals_its_three_steps(p, where, with_ws):
+    """lwe_dim = 0: the body alone -- no iteration, no key, and of the workspace only rot_t and the accumulator"""
+    check_bootstrap_steps(p, 64, where, with_ws, L=0, batch=2)
+
+
+def check_bootstrap_steps(p, n, where, with_ws, L, batch):
     torch = _torch()
     plan = make_plan(p, n)
-    L, k, beta, ell, batch = 4, 1, 7, 3, 5
+    k, beta, ell = 1, 7, 3
     rng = np.random.default_rng(seed("boot", p, n, where))
     lwe_a = random_words(rng, p, batch * (L + 1))
     lut_a = random_words(rng, p, (k + 1) * n)

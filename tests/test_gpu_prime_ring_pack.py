@@ -161,14 +161,18 @@ def test_merge_size_classes(p, n, k):
 @pytest.mark.parametrize("p", [P62, P32])
 def test_merge_on_the_host_path(p):
     torch = _torch()
-    n, k, beta, ell, batch = 64, 1, 6, 3, 3
+    n, beta, ell, batch = 64, 6, 3, 3
     plan = make_plan(p, n)
     rng = np.random.default_rng(seed("merge-host", p))
-    kw, kt = key_for(torch, plan, p, rng, k, ell, n)
-    E, O = (words_with_zeros(rng, p, batch * (k + 1) * n) for _ in range(2))
-    for shift, t, with_ws in ((n + 3, n + 1, True), (5, 5, False)):
-        got = run_merge(torch, plan, p, "host", E, O, kt, shift, t, k, beta, ell, with_ws)
-        assert np.array_equal(got, run_merge(torch, plan, p, "device", E, O, kt, shift, t, k, beta, ell)), (p, shift, t)
+    for k in (1, 0):   # glwe_dim = 0: no digits, no key, nothing of the workspace -- there the device path with one as well
+        kw, kt = key_for(torch, plan, p, rng, k, ell, n)
+        E, O = (words_with_zeros(rng, p, batch * (k + 1) * n) for _ in range(2))
+        for shift, t, with_ws in ((n + 3, n + 1, True), (5, 5, False)):
+            got = run_merge(torch, plan, p, "host", E, O, kt, shift, t, k, beta, ell, with_ws)
+            assert np.array_equal(got, run_merge(torch, plan, p, "device", E, O, kt, shift, t, k, beta, ell)), (p, k, shift, t)
+            if k == 0:
+                assert np.array_equal(got, compose_merge(torch, plan, p, E, O, kt, shift, t, k, beta, ell)), (p, shift, t)
+                assert np.array_equal(got, run_merge(torch, plan, p, "device", E, O, kt, shift, t, k, beta, ell, with_ws=True)), (p, shift, t)
 
 
 # -- 3. the whole packing ------------------------------------------------------------------------------------------------------------------
@@ -217,6 +221,7 @@ def test_ring_pack_equals_embed_merges_and_trace(p, n, k, batch):
             assert got.any() and np.array_equal(got, want), (p, n, k, m, with_ws, first_difference(got, want))
         if n == 32 and m == 8:
             assert np.array_equal(run_pack(torch, plan, p, "host", lwe, kt, m, k, beta, ell, batch, with_ws=True), want), (p, k, "host")
+            assert np.array_equal(run_pack(torch, plan, p, "host", lwe, kt, m, k, beta, ell, batch, with_ws=False), want), (p, k, "host, no workspace")
 
 
 @pytest.mark.parametrize("p,k", [(P62, 1), (P30, 2), (PM64, 0)])
