@@ -118,6 +118,11 @@ def lib():
             "glwe_merge_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
             "ring_pack_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
             "ring_pack_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, c_sz]),
+            # include/cntt_prime_cmux.h
+            "glwe_cmux_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
+            "glwe_cmux_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
+            "cmux_tree_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
+            "cmux_tree_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, c_sz]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, p + name)
@@ -168,6 +173,7 @@ def lib():
         "cntt_prime_multibit_grid": (ctypes.c_uint, [c_sz]),
         "cntt_prime_automorphism_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
         "cntt_prime_ring_pack_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
+        "cntt_prime_cmux_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
         # include/cntt_multibit.h
         "cntt_native_multibit_grid": (ctypes.c_uint, [c_sz]),
         "cntt_native_multibit_accumulate_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, c_sz, c_int, c_vp]),

@@ -406,6 +406,65 @@ class PrimePlan(PbsMixin):
         wp, wb = self._workspace(workspace, where)
         check(self._fn("ring_pack_batch")(self._h, op, ip, kp, lwe_count, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
 
+    # -- the CMux and the CMux tree against GGSW selectors mod p (include/cntt_prime_cmux.h) ------------------------------------------------
+    def glwe_cmux_workspace_bytes(self, glwe_dim, levels, batch):
+        """Bytes of workspace glwe_cmux_batch needs: the digit polynomials, rounded up to 256 bytes."""
+        if min(glwe_dim, batch) < 0 or levels <= 0:
+            raise Panic("glwe_dim and batch must not be negative, levels >= 1")
+        return self._fn("glwe_cmux_workspace_bytes")(self._h, glwe_dim, levels, batch)
+
+    def cmux_tree_workspace_bytes(self, lut_count, glwe_dim, levels, batch):
+        """Bytes of workspace cmux_tree_batch needs: the digits of the widest stage and two ciphertext buffers of batch*(lut_count/2) and
+        batch*(lut_count/4) ciphertexts, each rounded up to 256 bytes (0 for lut_count == 1)."""
+        if min(glwe_dim, batch) < 0 or levels <= 0 or lut_count <= 0:
+            raise Panic("glwe_dim and batch must not be negative, lut_count and levels >= 1")
+        return self._fn("cmux_tree_workspace_bytes")(self._h, lut_count, glwe_dim, levels, batch)
+
+    def glwe_cmux_batch(self, glwe_out, glwe0, glwe1, ggsw_ntt, glwe_dim, base_log, levels, workspace=None):
+        """glwe_out[b] = glwe0[b] + ExtProd(ggsw_ntt, glwe1[b] - glwe0[b]): glwe0[b] where the selector encrypts 0, glwe1[b] where it
+        encrypts 1.  The words of the copy of glwe0, gadget_decompose_batch(mode="plain") of the difference (digits not negated) and
+        external_product_batch(accumulate=True).  ggsw_ntt: ONE selector of (glwe_dim+1)*levels*(glwe_dim+1) NTT-domain polynomials in
+        the layout of one iteration's slice of bsk_ntt, shared by the batch; workspace: None (one allocation per call) or a buffer of
+        glwe_cmux_workspace_bytes()."""
+        op, oc, where, stream = self._words(glwe_out)
+        ap, ac, aw, _ = self._words(glwe0)
+        bp, bc, bw, _ = self._words(glwe1)
+        kp, kc, kw, _ = self._words(ggsw_ntt)
+        per = (glwe_dim + 1) * self._n
+        if glwe_dim < 0 or levels <= 0 or base_log <= 0 or ac % per or oc != ac or bc != ac or aw != where or bw != where:
+            raise Panic("glwe0, glwe1 and glwe_out: batch*(glwe_dim+1) polynomials each in the same memory; base_log, levels >= 1")
+        if kw != where or kc != (glwe_dim + 1) * levels * per:
+            raise Panic("ggsw_ntt: (glwe_dim+1)*levels*(glwe_dim+1) NTT-domain polynomials in the memory of the other buffers")
+        wp, wb = self._workspace(workspace, where)
+        check(self._fn("glwe_cmux_batch")(self._h, op, ap, bp, kp, glwe_dim, base_log, levels, ac // per, wp, wb, where, stream))
+
+    def cmux_tree_batch(self, glwe_out, lut_in, ggsw_ntt, lut_count, glwe_dim, base_log, levels, workspace=None):
+        """Selects one of lut_count (a power of two) PLAIN table polynomials per batch element by log2(lut_count) GGSW selectors:
+        glwe_out[b] = the trivial encryption of lut_in[b][a] plus noise, a = sum bit_i*2^i, selector i (address bit i, LSB first) at
+        polynomial i*(glwe_dim+1)*levels*(glwe_dim+1) of ggsw_ntt.  Stage 1 takes the table entries as they are (zero masks are never
+        decomposed), stages >= 2 are glwe_cmux_batch word for word; the top bit is consumed first.  lut_in: batch*lut_count
+        polynomials; glwe_out: batch*(glwe_dim+1) polynomials; ggsw_ntt may be None when lut_count == 1; workspace: None or a buffer of
+        cmux_tree_workspace_bytes()."""
+        ip, ic, where, stream = self._words(lut_in)
+        op, oc, ow, _ = self._words(glwe_out)
+        n = self._n
+        if glwe_dim < 0 or lut_count <= 0 or lut_count & (lut_count - 1) or levels <= 0 or base_log <= 0 or ic % (lut_count * n) or ow != where:
+            raise Panic("lut_in: batch*lut_count polynomials; glwe_out in the same memory; lut_count a power of two; base_log, levels >= 1")
+        batch = ic // (lut_count * n)
+        if oc != batch * (glwe_dim + 1) * n:
+            raise Panic("glwe_out must hold batch*(glwe_dim+1) = %d polynomials" % (batch * (glwe_dim + 1)))
+        kp = None
+        depth = lut_count.bit_length() - 1
+        if depth:
+            if ggsw_ntt is None:
+                raise Panic("ggsw_ntt may be None only when lut_count == 1")
+            kp, kc, kw, _ = self._words(ggsw_ntt)
+            if kw != where or kc != depth * (glwe_dim + 1) * levels * (glwe_dim + 1) * n:
+                raise Panic("ggsw_ntt: log2(lut_count) selectors of (glwe_dim+1)*levels*(glwe_dim+1) NTT-domain polynomials in the memory of "
+                            "the other buffers")
+        wp, wb = self._workspace(workspace, where)
+        check(self._fn("cmux_tree_batch")(self._h, op, ip, kp, lut_count, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
+
     # -- multi-bit blind rotation and bootstrap mod p (include/cntt_prime_multibit.h) ------------------------------------------------------
     #    multibit_pbs_workspace_bytes is PbsMixin's: no scratch here, so it equals pbs_workspace_bytes
     def multibit_accumulate_batch(self, out_ntt, terms_ntt, rot_rows, key_group, nterms, nout, grouping):
