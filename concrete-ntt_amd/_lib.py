@@ -123,6 +123,9 @@ def lib():
             "glwe_cmux_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
             "cmux_tree_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
             "cmux_tree_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, c_sz]),
+            # include/cntt_prime_cbs.h
+            "circuit_bootstrap_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz] + [ctypes.c_uint] * 6 + [c_sz, c_vp, c_sz, c_int, c_vp]),
+            "circuit_bootstrap_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, c_sz]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, p + name)
@@ -174,6 +177,7 @@ def lib():
         "cntt_prime_automorphism_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
         "cntt_prime_ring_pack_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
         "cntt_prime_cmux_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
+        "cntt_prime_cbs_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
         # include/cntt_multibit.h
         "cntt_native_multibit_grid": (ctypes.c_uint, [c_sz]),
         "cntt_native_multibit_accumulate_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, c_sz, c_int, c_vp]),

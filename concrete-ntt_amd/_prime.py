@@ -465,6 +465,43 @@ class PrimePlan(PbsMixin):
         wp, wb = self._workspace(workspace, where)
         check(self._fn("cmux_tree_batch")(self._h, op, ip, kp, lut_count, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
 
+    # -- the circuit bootstrap from LWE bits to GGSW selectors mod p (include/cntt_prime_cbs.h) --------------------------------------------
+    def circuit_bootstrap_workspace_bytes(self, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch):
+        """Bytes of workspace circuit_bootstrap_batch needs: rot_t, the tables, the digits of the rotation and the accumulators of the
+        batch*cbs_levels bootstrap elements, their int32 keyswitch digits and the slab sums, each rounded up to 256 bytes."""
+        if min(lwe_dim, glwe_dim, batch) < 0 or min(pbs_levels, ks_levels, cbs_levels) <= 0:
+            raise Panic("lwe_dim, glwe_dim and batch must not be negative, pbs_levels, ks_levels and cbs_levels >= 1")
+        return self._fn("circuit_bootstrap_workspace_bytes")(self._h, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch)
+
+    def circuit_bootstrap_batch(self, ggsw_ntt_out, lwe_in, bsk_ntt, fpksk_ntt, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log,
+                                ks_levels, cbs_base_log, cbs_levels, workspace=None):
+        """LWE encryptions of bits (phase bit*(p+1)/2 + e) -> GGSW selectors in the NTT domain, the ggsw_ntt argument of
+        cmux_tree_batch: element b of lwe_in (batch*(lwe_dim+1) words) becomes selector b of ggsw_ntt_out
+        (batch*(glwe_dim+1)*cbs_levels*(glwe_dim+1) polynomials).  One bootstrap per level against the constant table -H_l, then the
+        functional keyswitch as a slot-wise digit x key sum against fpksk_ntt: glwe_dim+1 keys of
+        (glwe_dim*n+1)*ks_levels*(glwe_dim+1) NTT-domain polynomials holding n^-1 * fwd(key).  bsk_ntt as in bootstrap_batch (None when
+        lwe_dim == 0); workspace: None (one allocation per call) or a buffer of circuit_bootstrap_workspace_bytes()."""
+        ip, ic, where, stream = self._words(lwe_in)
+        op, oc, ow, _ = self._words(ggsw_ntt_out)
+        n = self._n
+        if min(lwe_dim, glwe_dim) < 0 or min(pbs_base_log, pbs_levels, ks_base_log, ks_levels, cbs_base_log, cbs_levels) <= 0 \
+                or ic % (lwe_dim + 1) or ow != where:
+            raise Panic("lwe_in: batch*(lwe_dim+1) words; ggsw_ntt_out in the same memory; every base_log and levels >= 1")
+        batch = ic // (lwe_dim + 1)
+        if oc != batch * (glwe_dim + 1) * cbs_levels * (glwe_dim + 1) * n:
+            raise Panic("ggsw_ntt_out must hold batch*(glwe_dim+1)*cbs_levels*(glwe_dim+1) = %d polynomials"
+                        % (batch * (glwe_dim + 1) * cbs_levels * (glwe_dim + 1)))
+        if lwe_dim and bsk_ntt is None:
+            raise Panic("bsk_ntt may be None only when lwe_dim == 0")
+        kp = self._bsk(bsk_ntt, where, lwe_dim, glwe_dim, pbs_levels) if lwe_dim else None
+        fp, fc, fw, _ = self._words(fpksk_ntt)
+        if fw != where or fc != (glwe_dim + 1) * (glwe_dim * n + 1) * ks_levels * (glwe_dim + 1) * n:
+            raise Panic("fpksk_ntt: (glwe_dim+1) keys of (glwe_dim*n+1)*ks_levels*(glwe_dim+1) NTT-domain polynomials in the memory of the "
+                        "other buffers")
+        wp, wb = self._workspace(workspace, where)
+        check(self._fn("circuit_bootstrap_batch")(self._h, op, ip, kp, fp, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log, ks_levels,
+                                                  cbs_base_log, cbs_levels, batch, wp, wb, where, stream))
+
     # -- multi-bit blind rotation and bootstrap mod p (include/cntt_prime_multibit.h) ------------------------------------------------------
     #    multibit_pbs_workspace_bytes is PbsMixin's: no scratch here, so it equals pbs_workspace_bytes
     def multibit_accumulate_batch(self, out_ntt, terms_ntt, rot_rows, key_group, nterms, nout, grouping):
