@@ -186,6 +186,12 @@ def lib():
         "cntt_native_multibit_bootstrap_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint,
                                                          ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
         "cntt_native_multibit_pbs_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz]),
+        # include/cntt_cmux.h
+        "cntt_native_glwe_cmux_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
+        "cntt_native_glwe_cmux_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
+        "cntt_native_cmux_tree_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
+        "cntt_native_cmux_tree_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, c_sz]),
+        "cntt_native_cmux_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
         "cntt_product_plan_new": (c_int, [c_sz, c_u64, c_vp, c_sz, c_vp]),
         "cntt_product_plan_clone": (c_vp, [c_vp]),
         "cntt_product_plan_free": (None, [c_vp]),

@@ -375,6 +375,60 @@ class NativePlan(PbsMixin):
         allocation per call)."""
         self._bootstrap(lwe_out, lwe_in, lut, bsk_mb, lwe_dim, glwe_dim, base_log, levels, workspace, lut_per_element, grouping)
 
+    # -- the CMux and the CMux tree against GGSW selectors (include/cntt_cmux.h) ---------------------------------------------------------
+    def glwe_cmux_workspace_bytes(self, glwe_dim, levels, batch):
+        """Bytes of workspace glwe_cmux_batch needs: the digit polynomials, rounded up to 256 bytes."""
+        if min(glwe_dim, batch) < 0 or levels <= 0:
+            raise Panic("glwe_dim and batch must not be negative, levels >= 1")
+        return lib().cntt_native_glwe_cmux_workspace_bytes(self._h, glwe_dim, levels, batch)
+
+    def cmux_tree_workspace_bytes(self, lut_count, glwe_dim, levels, batch):
+        """Bytes of workspace cmux_tree_batch needs: the digits of the widest stage and two ciphertext buffers of batch*(lut_count/2) and
+        batch*(lut_count/4) ciphertexts, each rounded up to 256 bytes (0 for lut_count == 1)."""
+        if min(glwe_dim, batch) < 0 or levels <= 0 or lut_count <= 0:
+            raise Panic("glwe_dim and batch must not be negative, lut_count and levels >= 1")
+        return lib().cntt_native_cmux_tree_workspace_bytes(self._h, lut_count, glwe_dim, levels, batch)
+
+    def glwe_cmux_batch(self, glwe_out, glwe0, glwe1, ggsw_residues, glwe_dim, base_log, levels, workspace=None):
+        """glwe_out[b] = glwe0[b] + ExtProd(ggsw, glwe1[b] - glwe0[b]) mod 2^w: glwe0[b] where the selector encrypts 0, glwe1[b] where it
+        encrypts 1.  The words of the copy of glwe0, gadget_decompose_batch(mode="plain") of the difference and
+        external_product_batch(accumulate=True).  ggsw_residues: ONE selector as NPRIMES buffers of (glwe_dim+1)*levels*(glwe_dim+1)
+        residue polynomials as fwd_batch writes them, the layout of one iteration's slice of the bootstrapping key, shared by the batch;
+        workspace: None (one allocation per call) or a buffer of glwe_cmux_workspace_bytes()."""
+        op, oc, where, stream = self._words(glwe_out)
+        ap, ac, aw, _ = self._words(glwe0)
+        bp, bc, bw, _ = self._words(glwe1)
+        per = (glwe_dim + 1) * self._n
+        if glwe_dim < 0 or levels <= 0 or base_log <= 0 or ac % per or oc != ac or bc != ac or aw != where or bw != where:
+            raise Panic("glwe0, glwe1 and glwe_out: batch*(glwe_dim+1) polynomials each in the same memory; base_log, levels >= 1")
+        keys = self._planes(ggsw_residues, where, (glwe_dim + 1) * levels * per, "ggsw")
+        wp, wb = self._workspace(workspace, where)
+        check(lib().cntt_native_glwe_cmux_batch(self._h, op, ap, bp, keys, glwe_dim, base_log, levels, ac // per, wp, wb, where, stream))
+
+    def cmux_tree_batch(self, glwe_out, lut_in, ggsw_residues, lut_count, glwe_dim, base_log, levels, workspace=None):
+        """Selects one of lut_count (a power of two) PLAIN table polynomials per batch element by log2(lut_count) GGSW selectors:
+        glwe_out[b] = the trivial encryption of lut_in[b][a] plus noise, a = sum bit_i*2^i, selector i (address bit i, LSB first) at
+        residue polynomial i*(glwe_dim+1)*levels*(glwe_dim+1) of every buffer of ggsw_residues.  Stage 1 takes the table entries as they
+        are (zero masks are never decomposed), stages >= 2 are glwe_cmux_batch word for word; the top bit is consumed first.  lut_in:
+        batch*lut_count polynomials; glwe_out: batch*(glwe_dim+1) polynomials; ggsw_residues may be None when lut_count == 1; workspace:
+        None or a buffer of cmux_tree_workspace_bytes()."""
+        ip, ic, where, stream = self._words(lut_in)
+        op, oc, ow, _ = self._words(glwe_out)
+        n = self._n
+        if glwe_dim < 0 or lut_count <= 0 or lut_count & (lut_count - 1) or levels <= 0 or base_log <= 0 or ic % (lut_count * n) or ow != where:
+            raise Panic("lut_in: batch*lut_count polynomials; glwe_out in the same memory; lut_count a power of two; base_log, levels >= 1")
+        batch = ic // (lut_count * n)
+        if oc != batch * (glwe_dim + 1) * n:
+            raise Panic("glwe_out must hold batch*(glwe_dim+1) = %d polynomials" % (batch * (glwe_dim + 1)))
+        keys = None
+        depth = lut_count.bit_length() - 1
+        if depth:
+            if ggsw_residues is None:
+                raise Panic("ggsw_residues may be None only when lut_count == 1")
+            keys = self._planes(ggsw_residues, where, depth * (glwe_dim + 1) * levels * (glwe_dim + 1) * n, "ggsw")
+        wp, wb = self._workspace(workspace, where)
+        check(lib().cntt_native_cmux_tree_batch(self._h, op, ip, keys, lut_count, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
+
 
 def _make(kind, nprimes, word, res, binary, doc):
     return type("Plan", (NativePlan,), {"KIND": kind, "NPRIMES": nprimes, "WORD": word, "RES": res,

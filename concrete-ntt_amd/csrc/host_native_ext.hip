@@ -3,7 +3,8 @@
 // the programmable bootstrap (include/cntt_pbs.h), the LWE keyswitch and keyswitch + bootstrap (include/cntt_keyswitch.h), the
 // LWE-to-GLWE packing keyswitch (include/cntt_pack.h), the multi-bit blind rotation and bootstrap (include/cntt_multibit.h).  The last
 // four are the templates of pbs_host.hpp, lwe_host.hpp and multibit_host.hpp, shared with the prime plans: here are the family struct that
-// fits them to the native plans (NativePbs) and the C ABI over them (the multi-bit part: host_native_multibit.inc).
+// fits them to the native plans (NativePbs) and the C ABI over them (the multi-bit part: host_native_multibit.inc).  The CMux and the
+// CMux tree against GGSW selectors (include/cntt_cmux.h) are host_native_cmux.inc, over the same struct.
 #include <cstdio>
 
 #include "host_common.hpp"
@@ -448,3 +449,8 @@ extern "C" int cntt_native_pack_keyswitch_batch(const cntt_native_t *pl, void *g
 // multi-bit blind rotation and bootstrap (include/cntt_multibit.h, native_multibit.hpp)
 // ---------------------------------------------------------------------------------------------
 #include "host_native_multibit.inc"
+
+// ---------------------------------------------------------------------------------------------
+// the CMux and the CMux tree against GGSW selectors (include/cntt_cmux.h, native_cmux.hpp)
+// ---------------------------------------------------------------------------------------------
+#include "host_native_cmux.inc"
