@@ -429,6 +429,42 @@ class NativePlan(PbsMixin):
         wp, wb = self._workspace(workspace, where)
         check(lib().cntt_native_cmux_tree_batch(self._h, op, ip, keys, lut_count, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
 
+    # -- the circuit bootstrap from LWE bits to GGSW selectors (include/cntt_cbs.h) ------------------------------------------------------
+    def circuit_bootstrap_workspace_bytes(self, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch):
+        """Bytes of workspace circuit_bootstrap_batch needs: rot_t, the tables, the digits of the rotation and the accumulators of the
+        batch*cbs_levels bootstrap elements, their int32 keyswitch digits, the slab sums and the selector words, each rounded up to 256
+        bytes."""
+        if min(lwe_dim, glwe_dim, batch) < 0 or min(pbs_levels, ks_levels, cbs_levels) <= 0:
+            raise Panic("lwe_dim, glwe_dim and batch must not be negative, pbs_levels, ks_levels and cbs_levels >= 1")
+        return lib().cntt_native_circuit_bootstrap_workspace_bytes(self._h, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch)
+
+    def circuit_bootstrap_batch(self, ggsw_residues_out, lwe_in, bsk_residues, fpksk, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log,
+                                ks_levels, cbs_base_log, cbs_levels, workspace=None):
+        """LWE encryptions of bits (phase bit*2^(w-1) + e) -> GGSW selectors as residue planes, the ggsw_residues argument of
+        cmux_tree_batch: element b of lwe_in (batch*(lwe_dim+1) words) becomes selector b of every buffer of ggsw_residues_out (NPRIMES
+        buffers of batch*(glwe_dim+1)*cbs_levels*(glwe_dim+1) residue polynomials, written only).  One bootstrap per level against the
+        constant table -H_l, then the functional keyswitch as a wrapping digit x key sum against fpksk: glwe_dim+1 keys of
+        (glwe_dim*n+1)*ks_levels*(glwe_dim+1) polynomials of PLAIN words in the coefficient domain, 16-byte aligned; then fwd_batch.
+        bsk_residues as in bootstrap_batch (None when lwe_dim == 0); workspace: None (one allocation per call) or a buffer of
+        circuit_bootstrap_workspace_bytes().  Not on the binary kinds."""
+        ip, ic, where, stream = self._words(lwe_in)
+        n = self._n
+        if min(lwe_dim, glwe_dim) < 0 or min(pbs_base_log, pbs_levels, ks_base_log, ks_levels, cbs_base_log, cbs_levels) <= 0 \
+                or ic % (lwe_dim + 1):
+            raise Panic("lwe_in: batch*(lwe_dim+1) words; every base_log and levels >= 1")
+        batch = ic // (lwe_dim + 1)
+        outs = self._planes(ggsw_residues_out, where, batch * (glwe_dim + 1) * cbs_levels * (glwe_dim + 1) * n, "ggsw_residues_out")
+        if lwe_dim and bsk_residues is None:
+            raise Panic("bsk_residues may be None only when lwe_dim == 0")
+        keys = self._bsk(bsk_residues, where, lwe_dim, glwe_dim, pbs_levels) if lwe_dim else None
+        fp, fc, fw, _ = self._words(fpksk)
+        if fw != where or fc != (glwe_dim + 1) * (glwe_dim * n + 1) * ks_levels * (glwe_dim + 1) * n:
+            raise Panic("fpksk: (glwe_dim+1) keys of (glwe_dim*n+1)*ks_levels*(glwe_dim+1) polynomials of words in the memory of the other "
+                        "buffers")
+        wp, wb = self._workspace(workspace, where)
+        check(lib().cntt_native_circuit_bootstrap_batch(self._h, outs, ip, keys, fp, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log,
+                                                        ks_levels, cbs_base_log, cbs_levels, batch, wp, wb, where, stream))
+
 
 def _make(kind, nprimes, word, res, binary, doc):
     return type("Plan", (NativePlan,), {"KIND": kind, "NPRIMES": nprimes, "WORD": word, "RES": res,

@@ -4,7 +4,8 @@
 // LWE-to-GLWE packing keyswitch (include/cntt_pack.h), the multi-bit blind rotation and bootstrap (include/cntt_multibit.h).  The last
 // four are the templates of pbs_host.hpp, lwe_host.hpp and multibit_host.hpp, shared with the prime plans: here are the family struct that
 // fits them to the native plans (NativePbs) and the C ABI over them (the multi-bit part: host_native_multibit.inc).  The CMux and the
-// CMux tree against GGSW selectors (include/cntt_cmux.h) are host_native_cmux.inc, over the same struct.
+// CMux tree against GGSW selectors (include/cntt_cmux.h) are host_native_cmux.inc, over the same struct, and the circuit bootstrap that
+// makes such selectors from LWE bits (include/cntt_cbs.h) is host_native_cbs.inc.
 #include <cstdio>
 
 #include "host_common.hpp"
@@ -454,3 +455,8 @@ extern "C" int cntt_native_pack_keyswitch_batch(const cntt_native_t *pl, void *g
 // the CMux and the CMux tree against GGSW selectors (include/cntt_cmux.h, native_cmux.hpp)
 // ---------------------------------------------------------------------------------------------
 #include "host_native_cmux.inc"
+
+// ---------------------------------------------------------------------------------------------
+// the circuit bootstrap from LWE bits to GGSW selectors (include/cntt_cbs.h, native_cbs.hpp)
+// ---------------------------------------------------------------------------------------------
+#include "host_native_cbs.inc"
