@@ -192,6 +192,15 @@ def lib():
         "cntt_native_cmux_tree_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
         "cntt_native_cmux_tree_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, c_sz]),
         "cntt_native_cmux_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
+        # include/cntt_automorphism.h
+        "cntt_native_automorphism_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, c_int, c_vp]),
+        "cntt_native_automorphism_ntt_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, c_int, c_vp]),
+        "cntt_native_glwe_automorphism_keyswitch_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_int, c_sz, c_vp, c_sz,
+                                                                  c_int, c_vp]),
+        "cntt_native_glwe_automorphism_keyswitch_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
+        "cntt_native_glwe_trace_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
+        "cntt_native_glwe_trace_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
+        "cntt_native_automorphism_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
         # include/cntt_cbs.h
         "cntt_native_circuit_bootstrap_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz] + [ctypes.c_uint] * 6 + [c_sz, c_vp, c_sz, c_int, c_vp]),
         "cntt_native_circuit_bootstrap_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, c_sz]),

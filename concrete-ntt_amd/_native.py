@@ -429,6 +429,78 @@ class NativePlan(PbsMixin):
         wp, wb = self._workspace(workspace, where)
         check(lib().cntt_native_cmux_tree_batch(self._h, op, ip, keys, lut_count, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
 
+    # -- ring automorphism, Galois keyswitch and trace (include/cntt_automorphism.h) -----------------------------------------------------
+    def automorphism_batch(self, out, inp, t):
+        """out = sigma_t(inp): X -> X^t on coefficient-domain polynomials mod 2^w, t odd and below 2n.  inp, out: the same number of
+        polynomials in the same memory; out is only written and may not overlap inp."""
+        op, oc, where, stream = self._words(out)
+        ip, ic, iw, _ = self._words(inp)
+        if oc % self._n or ic != oc or iw != where or t < 0:
+            raise Panic("out and inp: the same whole number of polynomials in the same memory; t >= 0")
+        check(lib().cntt_native_automorphism_batch(self._h, op, ip, t, 1, oc // self._n, where, stream))
+
+    def automorphism_ntt_batch(self, out_residues, in_residues, t):
+        """The same map as a slot permutation of every residue plane: NPRIMES buffers in, NPRIMES buffers out, each of the same whole
+        number of residue polynomials.  inv_batch of the result is sigma_t of what the planes stand for."""
+        if len(in_residues) != self.NPRIMES or len(out_residues) != self.NPRIMES:
+            raise Panic("expected %d residue buffers in and out" % self.NPRIMES)
+        _, count, _, where, stream = buffer_info(out_residues[0])
+        if count % self._n or t < 0:
+            raise Panic("residue buffers: a whole number of residue polynomials; t >= 0")
+        outs = self._planes(out_residues, where, count, "out")
+        ins = self._planes(in_residues, where, count, "in")
+        check(lib().cntt_native_automorphism_ntt_batch(self._h, outs, ins, t, 1, count // self._n, where, stream))
+
+    def glwe_automorphism_keyswitch_workspace_bytes(self, glwe_dim, levels, batch):
+        """Bytes of workspace glwe_automorphism_keyswitch_batch needs: the negated digit polynomials, rounded up to 256 bytes."""
+        if min(glwe_dim, batch) < 0 or levels <= 0:
+            raise Panic("glwe_dim and batch must not be negative, levels >= 1")
+        return lib().cntt_native_glwe_automorphism_keyswitch_workspace_bytes(self._h, glwe_dim, levels, batch)
+
+    def glwe_trace_workspace_bytes(self, glwe_dim, levels, batch):
+        """Bytes of workspace glwe_trace_batch needs: the negated digit polynomials and a second ciphertext batch, each rounded up to 256
+        bytes."""
+        if min(glwe_dim, batch) < 0 or levels <= 0:
+            raise Panic("glwe_dim and batch must not be negative, levels >= 1")
+        return lib().cntt_native_glwe_trace_workspace_bytes(self._h, glwe_dim, levels, batch)
+
+    def _autoks(self, glwe_out, glwe_in, ak_residues, keys_count, glwe_dim, base_log, levels):
+        op, oc, where, stream = self._words(glwe_out)
+        ip, ic, iw, _ = self._words(glwe_in)
+        per = (glwe_dim + 1) * self._n
+        if glwe_dim < 0 or levels <= 0 or base_log <= 0 or ic % per or oc != ic or iw != where:
+            raise Panic("glwe_in and glwe_out: batch*(glwe_dim+1) polynomials each in the same memory; base_log, levels >= 1")
+        keys = None
+        if glwe_dim and keys_count:
+            if ak_residues is None:
+                raise Panic("ak_residues may be None only when glwe_dim == 0 (or steps == 0)")
+            keys = self._planes(ak_residues, where, keys_count * glwe_dim * levels * per, "ak")
+        return op, ip, keys, ic // per, where, stream
+
+    def glwe_automorphism_keyswitch_batch(self, glwe_out, glwe_in, ak_residues, t, glwe_dim, base_log, levels, add_input=False, workspace=None):
+        """The Galois keyswitch mod 2^w: glwe_out[b] = (glwe_in[b] if add_input) + the GLWE ciphertext under the same key of
+        sigma_t(phase(glwe_in[b])).  The words of the prefill, automorphism_batch on the masks, gadget_decompose_batch(mode="plain"), the
+        negation of the digits and external_product_batch(accumulate=True).  ak_residues: NPRIMES buffers of
+        glwe_dim*levels*(glwe_dim+1) residue polynomials as fwd_batch writes them (None when glwe_dim == 0); workspace: None (one
+        allocation per call) or a buffer of glwe_automorphism_keyswitch_workspace_bytes().  Not on the binary kinds."""
+        if t < 0:
+            raise Panic("t >= 0")
+        op, ip, keys, batch, where, stream = self._autoks(glwe_out, glwe_in, ak_residues, 1, glwe_dim, base_log, levels)
+        wp, wb = self._workspace(workspace, where)
+        check(lib().cntt_native_glwe_automorphism_keyswitch_batch(self._h, op, ip, keys, t, glwe_dim, base_log, levels, 1 if add_input else 0, batch,
+                                                                  wp, wb, where, stream))
+
+    def glwe_trace_batch(self, glwe_out, glwe_in, ak_residues, steps, glwe_dim, base_log, levels, workspace=None):
+        """`steps` <= log2 n stages cur <- cur + AutoKS_(n/2^r + 1)(cur): coefficient i of the phase becomes 2^steps*phase[i] mod 2^w where
+        2^steps divides i and 0 elsewhere (plus keyswitch noise) -- 2^steps is not a unit mod 2^w, so encode with `steps` bits of headroom
+        below the message.  ak_residues: NPRIMES buffers of steps*glwe_dim*levels*(glwe_dim+1) residue polynomials, key r at polynomial
+        r*glwe_dim*levels*(glwe_dim+1); workspace: None or a buffer of glwe_trace_workspace_bytes()."""
+        if steps < 0:
+            raise Panic("steps >= 0")
+        op, ip, keys, batch, where, stream = self._autoks(glwe_out, glwe_in, ak_residues, steps, glwe_dim, base_log, levels)
+        wp, wb = self._workspace(workspace, where)
+        check(lib().cntt_native_glwe_trace_batch(self._h, op, ip, keys, steps, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
+
     # -- the circuit bootstrap from LWE bits to GGSW selectors (include/cntt_cbs.h) ------------------------------------------------------
     def circuit_bootstrap_workspace_bytes(self, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch):
         """Bytes of workspace circuit_bootstrap_batch needs: rot_t, the tables, the digits of the rotation and the accumulators of the

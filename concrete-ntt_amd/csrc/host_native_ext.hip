@@ -5,7 +5,8 @@
 // four are the templates of pbs_host.hpp, lwe_host.hpp and multibit_host.hpp, shared with the prime plans: here are the family struct that
 // fits them to the native plans (NativePbs) and the C ABI over them (the multi-bit part: host_native_multibit.inc).  The CMux and the
 // CMux tree against GGSW selectors (include/cntt_cmux.h) are host_native_cmux.inc, over the same struct, and the circuit bootstrap that
-// makes such selectors from LWE bits (include/cntt_cbs.h) is host_native_cbs.inc.
+// makes such selectors from LWE bits (include/cntt_cbs.h) is host_native_cbs.inc.  The ring automorphism, the Galois keyswitch and the trace
+// (include/cntt_automorphism.h) are host_native_automorphism.inc.
 #include <cstdio>
 
 #include "host_common.hpp"
@@ -460,3 +461,8 @@ extern "C" int cntt_native_pack_keyswitch_batch(const cntt_native_t *pl, void *g
 // the circuit bootstrap from LWE bits to GGSW selectors (include/cntt_cbs.h, native_cbs.hpp)
 // ---------------------------------------------------------------------------------------------
 #include "host_native_cbs.inc"
+
+// ---------------------------------------------------------------------------------------------
+// the ring automorphism X -> X^t, the Galois keyswitch and the trace (include/cntt_automorphism.h, native_automorphism.hpp)
+// ---------------------------------------------------------------------------------------------
+#include "host_native_automorphism.inc"
