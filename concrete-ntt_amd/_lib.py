@@ -201,6 +201,14 @@ def lib():
         "cntt_native_glwe_trace_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
         "cntt_native_glwe_trace_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
         "cntt_native_automorphism_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
+        # include/cntt_ring_pack.h
+        "cntt_native_glwe_embed_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_int, c_vp]),
+        "cntt_native_glwe_merge_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int,
+                                                 c_vp]),
+        "cntt_native_glwe_merge_workspace_bytes": (c_sz, [c_vp, c_sz, ctypes.c_uint, c_sz]),
+        "cntt_native_ring_pack_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, c_sz, c_vp, c_sz, c_int, c_vp]),
+        "cntt_native_ring_pack_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, c_sz]),
+        "cntt_native_ring_pack_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
         # include/cntt_cbs.h
         "cntt_native_circuit_bootstrap_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz] + [ctypes.c_uint] * 6 + [c_sz, c_vp, c_sz, c_int, c_vp]),
         "cntt_native_circuit_bootstrap_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, c_sz]),

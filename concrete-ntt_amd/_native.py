@@ -501,6 +501,68 @@ class NativePlan(PbsMixin):
         wp, wb = self._workspace(workspace, where)
         check(lib().cntt_native_glwe_trace_batch(self._h, op, ip, keys, steps, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
 
+    # -- ring packing of LWE ciphertexts through automorphisms (include/cntt_ring_pack.h) -------------------------------------------------
+    def glwe_merge_workspace_bytes(self, glwe_dim, levels, batch):
+        """Bytes of workspace glwe_merge_batch needs: the negated digit polynomials, rounded up to 256 bytes."""
+        if min(glwe_dim, batch) < 0 or levels <= 0:
+            raise Panic("glwe_dim and batch must not be negative, levels >= 1")
+        return lib().cntt_native_glwe_merge_workspace_bytes(self._h, glwe_dim, levels, batch)
+
+    def ring_pack_workspace_bytes(self, lwe_count, glwe_dim, levels, batch):
+        """Bytes of workspace ring_pack_batch needs: the digits of the widest stage and two ciphertext buffers of
+        batch*max(lwe_count/2, 1) and batch*max(lwe_count/4, 1) ciphertexts, each rounded up to 256 bytes."""
+        if min(glwe_dim, batch) < 0 or levels <= 0 or lwe_count <= 0:
+            raise Panic("glwe_dim and batch must not be negative, lwe_count and levels >= 1")
+        return lib().cntt_native_ring_pack_workspace_bytes(self._h, lwe_count, glwe_dim, levels, batch)
+
+    def glwe_embed_batch(self, glwe_out, lwe_in, glwe_dim):
+        """The inverse of sample_extract_batch(index=0): glwe[q][0] = lwe[q*n], glwe[q][i] = -lwe[q*n + n - i] mod 2^w, body
+        (lwe[glwe_dim*n], 0, ..., 0).  lwe_in: batch*(glwe_dim*n + 1) words; glwe_out: batch*(glwe_dim + 1) polynomials, only written.
+        Every kind."""
+        ip, ic, where, stream = self._words(lwe_in)
+        op, oc, ow, _ = self._words(glwe_out)
+        n = self._n
+        if glwe_dim < 0 or ic % (glwe_dim * n + 1) or ow != where or oc != ic // (glwe_dim * n + 1) * (glwe_dim + 1) * n:
+            raise Panic("lwe_in: batch*(glwe_dim*n+1) words; glwe_out: batch*(glwe_dim+1) polynomials in the same memory")
+        check(lib().cntt_native_glwe_embed_batch(self._h, op, ip, glwe_dim, ic // (glwe_dim * n + 1), where, stream))
+
+    def glwe_merge_batch(self, glwe_out, glwe_even, glwe_odd, ak_residues, shift, t, glwe_dim, base_log, levels, workspace=None):
+        """One node of the packing tree: glwe_out[b] = a + AutoKS_t(d) with a = even[b] + X^shift odd[b], d = even[b] - X^shift odd[b]
+        mod 2^w; the words of the prefill (a, body plus sigma_t(d body)), the negated digits of sigma_t(d mask) and
+        external_product_batch(accumulate=True) against the ONE key ak_residues of glwe_automorphism_keyswitch_batch's layout (None when
+        glwe_dim == 0).  0 <= shift < 2n, t odd below 2n; workspace: None (one allocation per call) or a buffer of
+        glwe_merge_workspace_bytes().  Not on the binary kinds."""
+        op, ep, keys, batch, where, stream = self._autoks(glwe_out, glwe_even, ak_residues, 1, glwe_dim, base_log, levels)
+        dp, dc, dw, _ = self._words(glwe_odd)
+        if dw != where or dc != batch * (glwe_dim + 1) * self._n or shift < 0 or t < 0:
+            raise Panic("glwe_odd: batch*(glwe_dim+1) polynomials in the memory of the other buffers; shift, t >= 0")
+        wp, wb = self._workspace(workspace, where)
+        check(lib().cntt_native_glwe_merge_batch(self._h, op, ep, dp, keys, shift, t, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
+
+    def ring_pack_batch(self, glwe_out, lwe_in, ak_residues, lwe_count, glwe_dim, base_log, levels, workspace=None):
+        """Packs lwe_count (a power of two <= n) LWE ciphertexts of glwe_dim*n + 1 words, encrypted under the flattened GLWE key, into one
+        GLWE ciphertext: glwe_embed_batch, log2(lwe_count) stages of glwe_merge_batch (shift n/2^s, t = 2^s + 1, key log2(n) - s) and
+        glwe_trace_batch with log2(n) - log2(lwe_count) steps, word for word.  MESSAGE j SITS AT COEFFICIENT j*n/lwe_count (a strided
+        layout) and carries the factor n: the phase there is n*phase(lwe_j) mod 2^w and every other coefficient is 0 with noise-free keys.
+        n is not a unit mod 2^w: encode with log2(n) bits of headroom below the message.  lwe_in: batch*lwe_count*(glwe_dim*n + 1) words;
+        glwe_out: batch*(glwe_dim+1) polynomials; ak_residues: NPRIMES buffers of all log2(n) trace keys back to back (None when
+        glwe_dim == 0); workspace: None or a buffer of ring_pack_workspace_bytes().  Not on the binary kinds."""
+        ip, ic, where, stream = self._words(lwe_in)
+        op, oc, ow, _ = self._words(glwe_out)
+        n = self._n
+        if glwe_dim < 0 or lwe_count <= 0 or levels <= 0 or base_log <= 0 or ic % (lwe_count * (glwe_dim * n + 1)) or ow != where:
+            raise Panic("lwe_in: batch*lwe_count*(glwe_dim*n+1) words; glwe_out in the same memory; lwe_count, base_log, levels >= 1")
+        batch = ic // (lwe_count * (glwe_dim * n + 1))
+        if oc != batch * (glwe_dim + 1) * n:
+            raise Panic("glwe_out must hold batch*(glwe_dim+1) = %d polynomials" % (batch * (glwe_dim + 1)))
+        keys = None
+        if glwe_dim:
+            if ak_residues is None:
+                raise Panic("ak_residues may be None only when glwe_dim == 0")
+            keys = self._planes(ak_residues, where, (n.bit_length() - 1) * glwe_dim * levels * (glwe_dim + 1) * n, "ak")
+        wp, wb = self._workspace(workspace, where)
+        check(lib().cntt_native_ring_pack_batch(self._h, op, ip, keys, lwe_count, glwe_dim, base_log, levels, batch, wp, wb, where, stream))
+
     # -- the circuit bootstrap from LWE bits to GGSW selectors (include/cntt_cbs.h) ------------------------------------------------------
     def circuit_bootstrap_workspace_bytes(self, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch):
         """Bytes of workspace circuit_bootstrap_batch needs: rot_t, the tables, the digits of the rotation and the accumulators of the

@@ -6,7 +6,8 @@
 // fits them to the native plans (NativePbs) and the C ABI over them (the multi-bit part: host_native_multibit.inc).  The CMux and the
 // CMux tree against GGSW selectors (include/cntt_cmux.h) are host_native_cmux.inc, over the same struct, and the circuit bootstrap that
 // makes such selectors from LWE bits (include/cntt_cbs.h) is host_native_cbs.inc.  The ring automorphism, the Galois keyswitch and the trace
-// (include/cntt_automorphism.h) are host_native_automorphism.inc.
+// (include/cntt_automorphism.h) are host_native_automorphism.inc, and ring packing of LWE ciphertexts through them (include/cntt_ring_pack.h) is
+// host_native_ring_pack.inc.
 #include <cstdio>
 
 #include "host_common.hpp"
@@ -466,3 +467,8 @@ extern "C" int cntt_native_pack_keyswitch_batch(const cntt_native_t *pl, void *g
 // the ring automorphism X -> X^t, the Galois keyswitch and the trace (include/cntt_automorphism.h, native_automorphism.hpp)
 // ---------------------------------------------------------------------------------------------
 #include "host_native_automorphism.inc"
+
+// ---------------------------------------------------------------------------------------------
+// ring packing of LWE ciphertexts through automorphisms (include/cntt_ring_pack.h, native_ring_pack.hpp)
+// ---------------------------------------------------------------------------------------------
+#include "host_native_ring_pack.inc"
