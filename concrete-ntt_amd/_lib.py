@@ -126,6 +126,14 @@ def lib():
             # include/cntt_prime_cbs.h
             "circuit_bootstrap_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz] + [ctypes.c_uint] * 6 + [c_sz, c_vp, c_sz, c_int, c_vp]),
             "circuit_bootstrap_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, c_sz]),
+            # include/cntt_prime_manylut.h
+            "lwe_modswitch_manylut_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, c_sz, c_int, c_vp]),
+            "sample_extract_many_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, c_int, c_vp]),
+            "bootstrap_manylut_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
+                                                c_sz, c_sz, c_vp, c_sz, c_int, c_vp]),
+            "circuit_bootstrap_manylut_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz] + [ctypes.c_uint] * 7
+                                                + [c_sz, c_vp, c_sz, c_int, c_vp]),
+            "circuit_bootstrap_manylut_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, c_sz]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, p + name)
