@@ -221,6 +221,14 @@ def lib():
         "cntt_native_circuit_bootstrap_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz] + [ctypes.c_uint] * 6 + [c_sz, c_vp, c_sz, c_int, c_vp]),
         "cntt_native_circuit_bootstrap_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, c_sz]),
         "cntt_native_cbs_grid": (ctypes.c_uint, [c_sz, c_int, c_sz]),
+        # include/cntt_manylut.h
+        "cntt_native_lwe_modswitch_manylut_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, c_sz, c_int, c_vp]),
+        "cntt_native_sample_extract_many_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_sz, c_int, c_vp]),
+        "cntt_native_bootstrap_manylut_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint,
+                                                        ctypes.c_uint, c_sz, c_sz, c_vp, c_sz, c_int, c_vp]),
+        "cntt_native_circuit_bootstrap_manylut_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz] + [ctypes.c_uint] * 7
+                                                        + [c_sz, c_vp, c_sz, c_int, c_vp]),
+        "cntt_native_circuit_bootstrap_manylut_workspace_bytes": (c_sz, [c_vp, c_sz, c_sz, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, c_sz]),
         "cntt_product_plan_new": (c_int, [c_sz, c_u64, c_vp, c_sz, c_vp]),
         "cntt_product_plan_clone": (c_vp, [c_vp]),
         "cntt_product_plan_free": (None, [c_vp]),

@@ -472,3 +472,8 @@ extern "C" int cntt_native_pack_keyswitch_batch(const cntt_native_t *pl, void *g
 // ring packing of LWE ciphertexts through automorphisms (include/cntt_ring_pack.h, native_ring_pack.hpp)
 // ---------------------------------------------------------------------------------------------
 #include "host_native_ring_pack.inc"
+
+// ---------------------------------------------------------------------------------------------
+// the many-LUT bootstrap and the circuit bootstrap with one rotation per input bit (include/cntt_manylut.h, native_manylut.hpp)
+// ---------------------------------------------------------------------------------------------
+#include "host_native_manylut.inc"
