@@ -568,9 +568,30 @@ class NativePlan(PbsMixin):
         """Bytes of workspace circuit_bootstrap_batch needs: rot_t, the tables, the digits of the rotation and the accumulators of the
         batch*cbs_levels bootstrap elements, their int32 keyswitch digits, the slab sums and the selector words, each rounded up to 256
         bytes."""
-        if min(lwe_dim, glwe_dim, batch) < 0 or min(pbs_levels, ks_levels, cbs_levels) <= 0:
-            raise Panic("lwe_dim, glwe_dim and batch must not be negative, pbs_levels, ks_levels and cbs_levels >= 1")
-        return lib().cntt_native_circuit_bootstrap_workspace_bytes(self._h, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch)
+        return self._cbs_workspace_bytes("circuit_bootstrap_workspace_bytes", lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch)
+
+    def _circuit_bootstrap(self, ggsw_residues_out, lwe_in, bsk_residues, fpksk, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log,
+                           ks_levels, cbs_base_log, cbs_levels, workspace, log_lut_count=None):
+        """circuit_bootstrap_batch, and with a log_lut_count circuit_bootstrap_manylut_batch."""
+        one = () if log_lut_count is None else (log_lut_count,)
+        ip, ic, where, stream = self._words(lwe_in)
+        n = self._n
+        if min(lwe_dim, glwe_dim, *one) < 0 or min(pbs_base_log, pbs_levels, ks_base_log, ks_levels, cbs_base_log, cbs_levels) <= 0 \
+                or ic % (lwe_dim + 1):
+            raise Panic("lwe_in: batch*(lwe_dim+1) words; every base_log and levels >= 1" + ("; log_lut_count >= 0" if one else ""))
+        batch = ic // (lwe_dim + 1)
+        outs = self._planes(ggsw_residues_out, where, batch * (glwe_dim + 1) * cbs_levels * (glwe_dim + 1) * n, "ggsw_residues_out")
+        if lwe_dim and bsk_residues is None:
+            raise Panic("bsk_residues may be None only when lwe_dim == 0")
+        keys = self._bsk(bsk_residues, where, lwe_dim, glwe_dim, pbs_levels) if lwe_dim else None
+        fp, fc, fw, _ = self._words(fpksk)
+        if fw != where or fc != (glwe_dim + 1) * (glwe_dim * n + 1) * ks_levels * (glwe_dim + 1) * n:
+            raise Panic("fpksk: (glwe_dim+1) keys of (glwe_dim*n+1)*ks_levels*(glwe_dim+1) polynomials of words in the memory of the other "
+                        "buffers")
+        wp, wb = self._workspace(workspace, where)
+        call = self._fn("circuit_bootstrap_manylut_batch" if one else "circuit_bootstrap_batch")
+        check(call(self._h, outs, ip, keys, fp, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log, ks_levels, cbs_base_log, cbs_levels,
+                   *one, batch, wp, wb, where, stream))
 
     def circuit_bootstrap_batch(self, ggsw_residues_out, lwe_in, bsk_residues, fpksk, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log,
                                 ks_levels, cbs_base_log, cbs_levels, workspace=None):
@@ -581,76 +602,26 @@ class NativePlan(PbsMixin):
         (glwe_dim*n+1)*ks_levels*(glwe_dim+1) polynomials of PLAIN words in the coefficient domain, 16-byte aligned; then fwd_batch.
         bsk_residues as in bootstrap_batch (None when lwe_dim == 0); workspace: None (one allocation per call) or a buffer of
         circuit_bootstrap_workspace_bytes().  Not on the binary kinds."""
-        ip, ic, where, stream = self._words(lwe_in)
-        n = self._n
-        if min(lwe_dim, glwe_dim) < 0 or min(pbs_base_log, pbs_levels, ks_base_log, ks_levels, cbs_base_log, cbs_levels) <= 0 \
-                or ic % (lwe_dim + 1):
-            raise Panic("lwe_in: batch*(lwe_dim+1) words; every base_log and levels >= 1")
-        batch = ic // (lwe_dim + 1)
-        outs = self._planes(ggsw_residues_out, where, batch * (glwe_dim + 1) * cbs_levels * (glwe_dim + 1) * n, "ggsw_residues_out")
-        if lwe_dim and bsk_residues is None:
-            raise Panic("bsk_residues may be None only when lwe_dim == 0")
-        keys = self._bsk(bsk_residues, where, lwe_dim, glwe_dim, pbs_levels) if lwe_dim else None
-        fp, fc, fw, _ = self._words(fpksk)
-        if fw != where or fc != (glwe_dim + 1) * (glwe_dim * n + 1) * ks_levels * (glwe_dim + 1) * n:
-            raise Panic("fpksk: (glwe_dim+1) keys of (glwe_dim*n+1)*ks_levels*(glwe_dim+1) polynomials of words in the memory of the other "
-                        "buffers")
-        wp, wb = self._workspace(workspace, where)
-        check(lib().cntt_native_circuit_bootstrap_batch(self._h, outs, ip, keys, fp, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log,
-                                                        ks_levels, cbs_base_log, cbs_levels, batch, wp, wb, where, stream))
+        self._circuit_bootstrap(ggsw_residues_out, lwe_in, bsk_residues, fpksk, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log,
+                                ks_levels, cbs_base_log, cbs_levels, workspace)
 
     # -- the many-LUT bootstrap and the circuit bootstrap with one rotation per input bit (include/cntt_manylut.h) ----------------------
-    def lwe_modswitch_manylut_batch(self, rot_t, lwe, lwe_dim, log_lut_count):
-        """lwe_modswitch_batch with the coarse rule: every exponent is round(lwe[b][i] * 2n' / 2^w) mod 2n' (ties up) for
-        n' = n / 2^log_lut_count, shifted left by log_lut_count, so its low log_lut_count bits are clear; the body row negated mod 2n.
-        log_lut_count = 0 is lwe_modswitch_batch word for word."""
-        lp, lc, where, stream = self._words(lwe)
-        if lwe_dim < 0 or log_lut_count < 0 or lc % (lwe_dim + 1):
-            raise Panic("lwe: batch*(lwe_dim+1) words; rot_t: as many uint32 in the same memory; log_lut_count >= 0")
-        rp, rc_ = self._rot(rot_t, where, "rot_t")
-        if rc_ != lc:
-            raise Panic("lwe: batch*(lwe_dim+1) words; rot_t: as many uint32 in the same memory")
-        check(self._fn("lwe_modswitch_manylut_batch")(self._h, rp, lp, lwe_dim, log_lut_count, lc // (lwe_dim + 1), where, stream))
-
-    def sample_extract_many_batch(self, lwe_out, glwe, glwe_dim, count):
-        """lwe_out[b][h] = sample_extract_batch(glwe[b], index=h) for h < count, from one read of glwe: lwe_out holds
-        batch*count*(glwe_dim*n+1) words, glwe batch*(glwe_dim+1) polynomials; 1 <= count <= n."""
-        gp, gc, where, stream = self._words(glwe)
-        op, oc, ow, _ = self._words(lwe_out)
-        n = self._n
-        if glwe_dim < 0 or count <= 0 or gc % ((glwe_dim + 1) * n) or ow != where \
-                or oc != gc // ((glwe_dim + 1) * n) * count * (glwe_dim * n + 1):
-            raise Panic("glwe: batch*(glwe_dim+1) polynomials; lwe_out: batch*count*(glwe_dim*n+1) words in the same memory; count >= 1")
-        check(self._fn("sample_extract_many_batch")(self._h, op, gp, glwe_dim, count, gc // ((glwe_dim + 1) * n), where, stream))
-
+    #    lwe_modswitch_manylut_batch and sample_extract_many_batch are PbsMixin's
     def bootstrap_manylut_batch(self, lwe_out, lwe_in, lut, bsk_residues, lwe_dim, glwe_dim, base_log, levels, log_lut_count, lut_count,
                                 workspace=None, lut_per_element=None):
         """lwe_modswitch_manylut_batch -> blind_rotate_batch -> sample_extract_many_batch(count=lut_count) in one call: lut_count <=
         2^log_lut_count functions of every encrypted message for one rotation, function h at the coefficients m*2^log_lut_count + h of
         the table.  lwe_in: batch*(lwe_dim+1) words; lwe_out: batch*lut_count*(glwe_dim*n+1) words; workspace: None (one allocation per
         call) or a buffer of pbs_workspace_bytes()."""
-        ip, ic, where, stream = self._words(lwe_in)
-        op, oc, ow, _ = self._words(lwe_out)
-        n = self._n
-        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or log_lut_count < 0 or lut_count <= 0 or ic % (lwe_dim + 1) \
-                or ow != where:
-            raise Panic("lwe_in: batch*(lwe_dim+1) words; lwe_out in the same memory; base_log, levels, lut_count >= 1; log_lut_count >= 0")
-        batch = ic // (lwe_dim + 1)
-        if oc != batch * lut_count * (glwe_dim * n + 1):
-            raise Panic("lwe_out must hold batch*lut_count*(glwe_dim*n+1) = %d words" % (batch * lut_count * (glwe_dim * n + 1)))
-        lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
-        kp = self._bsk(bsk_residues, where, lwe_dim, glwe_dim, levels)
-        wp, wb = self._workspace(workspace, where)
-        check(self._fn("bootstrap_manylut_batch")(self._h, op, ip, lp, per, kp, lwe_dim, glwe_dim, base_log, levels, log_lut_count, lut_count,
-                                                  batch, wp, wb, where, stream))
+        self._bootstrap_manylut(lwe_out, lwe_in, lut, bsk_residues, lwe_dim, glwe_dim, base_log, levels, log_lut_count, lut_count, workspace,
+                                lut_per_element)
 
     def circuit_bootstrap_manylut_workspace_bytes(self, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch):
         """Bytes of workspace circuit_bootstrap_manylut_batch needs: rot_t, the shared table, the digits of the rotation and the
         accumulators of the batch elements, the int32 keyswitch digits, the slab sums and the selector words of the batch*cbs_levels
         selector rows, each rounded up to 256 bytes."""
-        if min(lwe_dim, glwe_dim, batch) < 0 or min(pbs_levels, ks_levels, cbs_levels) <= 0:
-            raise Panic("lwe_dim, glwe_dim and batch must not be negative, pbs_levels, ks_levels and cbs_levels >= 1")
-        return self._fn("circuit_bootstrap_manylut_workspace_bytes")(self._h, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch)
+        return self._cbs_workspace_bytes("circuit_bootstrap_manylut_workspace_bytes", lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels,
+                                         batch)
 
     def circuit_bootstrap_manylut_batch(self, ggsw_residues_out, lwe_in, bsk_residues, fpksk, lwe_dim, glwe_dim, pbs_base_log, pbs_levels,
                                         ks_base_log, ks_levels, cbs_base_log, cbs_levels, log_lut_count, workspace=None):
@@ -658,23 +629,8 @@ class NativePlan(PbsMixin):
         table, the modulus switch clears the low log_lut_count bits, and level l is extracted at the index l - 1.  cbs_levels <=
         2^log_lut_count <= n/2.  The buffers are those of circuit_bootstrap_batch; workspace: None (one allocation per call) or a buffer
         of circuit_bootstrap_manylut_workspace_bytes().  Not on the binary kinds."""
-        ip, ic, where, stream = self._words(lwe_in)
-        n = self._n
-        if min(lwe_dim, glwe_dim, log_lut_count) < 0 or min(pbs_base_log, pbs_levels, ks_base_log, ks_levels, cbs_base_log, cbs_levels) <= 0 \
-                or ic % (lwe_dim + 1):
-            raise Panic("lwe_in: batch*(lwe_dim+1) words; every base_log and levels >= 1; log_lut_count >= 0")
-        batch = ic // (lwe_dim + 1)
-        outs = self._planes(ggsw_residues_out, where, batch * (glwe_dim + 1) * cbs_levels * (glwe_dim + 1) * n, "ggsw_residues_out")
-        if lwe_dim and bsk_residues is None:
-            raise Panic("bsk_residues may be None only when lwe_dim == 0")
-        keys = self._bsk(bsk_residues, where, lwe_dim, glwe_dim, pbs_levels) if lwe_dim else None
-        fp, fc, fw, _ = self._words(fpksk)
-        if fw != where or fc != (glwe_dim + 1) * (glwe_dim * n + 1) * ks_levels * (glwe_dim + 1) * n:
-            raise Panic("fpksk: (glwe_dim+1) keys of (glwe_dim*n+1)*ks_levels*(glwe_dim+1) polynomials of words in the memory of the other "
-                        "buffers")
-        wp, wb = self._workspace(workspace, where)
-        check(self._fn("circuit_bootstrap_manylut_batch")(self._h, outs, ip, keys, fp, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log,
-                                                          ks_levels, cbs_base_log, cbs_levels, log_lut_count, batch, wp, wb, where, stream))
+        self._circuit_bootstrap(ggsw_residues_out, lwe_in, bsk_residues, fpksk, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log,
+                                ks_levels, cbs_base_log, cbs_levels, workspace, log_lut_count)
 
 
 def _make(kind, nprimes, word, res, binary, doc):

@@ -11,7 +11,9 @@ class PbsMixin:
     _bsk_mb(key, where, lwe_dim, glwe_dim, levels, grouping) -> the same for the multi-bit key;
     _fn(name) -> the C entry point `name` of the plan's family;
     blind_rotate_batch and bootstrap_batch, which name the key argument their way and pass on to _blind_rotate / _bootstrap, and their
-    multibit_* forms, which pass a `grouping` as well."""
+    multibit_* forms, which pass a `grouping` as well; bootstrap_manylut_batch, which does the same with _bootstrap_manylut;
+    the two circuit_bootstrap*_workspace_bytes, which say what their parts are and pass on to _cbs_workspace_bytes.  The circuit bootstrap
+    itself stays with the plan classes: its output, its keys and every message about them differ."""
 
     SRC_MODES = {"plain": 0, "rotate": 1, "cmux": 2}
 
@@ -142,3 +144,52 @@ class PbsMixin:
         key, call, g = self._key_call("bootstrap_batch", bsk, where, lwe_dim, glwe_dim, levels, grouping)
         wp, wb = self._workspace(workspace, where)
         check(call(self._h, op, ip, lp, per, key, lwe_dim, glwe_dim, base_log, levels, *g, batch, wp, wb, where, stream))
+
+    # -- the many-LUT calls (include/cntt_manylut.h, cntt_prime_manylut.h) ----------------------------------------------------------------
+    def lwe_modswitch_manylut_batch(self, rot_t, lwe, lwe_dim, log_lut_count):
+        """lwe_modswitch_batch with the coarse rule: every exponent is round(lwe[b][i] * 2n' / q) mod 2n' for n' = n / 2^log_lut_count
+        (q = 2^w with ties rounded up on the native plans, q = p on the prime plans), shifted left by log_lut_count, so its low
+        log_lut_count bits are clear; the body row negated mod 2n.  log_lut_count = 0 is lwe_modswitch_batch word for word."""
+        lp, lc, where, stream = self._words(lwe)
+        if lwe_dim < 0 or log_lut_count < 0 or lc % (lwe_dim + 1):
+            raise Panic("lwe: batch*(lwe_dim+1) words; rot_t: as many uint32 in the same memory; log_lut_count >= 0")
+        rp, rc_ = self._rot(rot_t, where, "rot_t")
+        if rc_ != lc:
+            raise Panic("lwe: batch*(lwe_dim+1) words; rot_t: as many uint32 in the same memory")
+        check(self._fn("lwe_modswitch_manylut_batch")(self._h, rp, lp, lwe_dim, log_lut_count, lc // (lwe_dim + 1), where, stream))
+
+    def sample_extract_many_batch(self, lwe_out, glwe, glwe_dim, count):
+        """lwe_out[b][h] = sample_extract_batch(glwe[b], index=h) for h < count, from one read of glwe: lwe_out holds
+        batch*count*(glwe_dim*n+1) words, glwe batch*(glwe_dim+1) polynomials; 1 <= count <= n."""
+        gp, gc, where, stream = self._words(glwe)
+        op, oc, ow, _ = self._words(lwe_out)
+        n = self._n
+        if glwe_dim < 0 or count <= 0 or gc % ((glwe_dim + 1) * n) or ow != where \
+                or oc != gc // ((glwe_dim + 1) * n) * count * (glwe_dim * n + 1):
+            raise Panic("glwe: batch*(glwe_dim+1) polynomials; lwe_out: batch*count*(glwe_dim*n+1) words in the same memory; count >= 1")
+        check(self._fn("sample_extract_many_batch")(self._h, op, gp, glwe_dim, count, gc // ((glwe_dim + 1) * n), where, stream))
+
+    def _bootstrap_manylut(self, lwe_out, lwe_in, lut, bsk, lwe_dim, glwe_dim, base_log, levels, log_lut_count, lut_count, workspace,
+                           lut_per_element):
+        """bootstrap_manylut_batch of the plan classes, which name the key."""
+        ip, ic, where, stream = self._words(lwe_in)
+        op, oc, ow, _ = self._words(lwe_out)
+        n = self._n
+        if lwe_dim < 0 or glwe_dim < 0 or levels <= 0 or base_log <= 0 or log_lut_count < 0 or lut_count <= 0 or ic % (lwe_dim + 1) \
+                or ow != where:
+            raise Panic("lwe_in: batch*(lwe_dim+1) words; lwe_out in the same memory; base_log, levels, lut_count >= 1; log_lut_count >= 0")
+        batch = ic // (lwe_dim + 1)
+        if oc != batch * lut_count * (glwe_dim * n + 1):
+            raise Panic("lwe_out must hold batch*lut_count*(glwe_dim*n+1) = %d words" % (batch * lut_count * (glwe_dim * n + 1)))
+        lp, per = self._lut(lut, lut_per_element, where, glwe_dim, batch)
+        kp = self._bsk(bsk, where, lwe_dim, glwe_dim, levels)
+        wp, wb = self._workspace(workspace, where)
+        check(self._fn("bootstrap_manylut_batch")(self._h, op, ip, lp, per, kp, lwe_dim, glwe_dim, base_log, levels, log_lut_count, lut_count,
+                                                  batch, wp, wb, where, stream))
+
+    def _cbs_workspace_bytes(self, name, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch):
+        """circuit_bootstrap_workspace_bytes and circuit_bootstrap_manylut_workspace_bytes (`name`) of the plan classes, which say what
+        the parts are."""
+        if min(lwe_dim, glwe_dim, batch) < 0 or min(pbs_levels, ks_levels, cbs_levels) <= 0:
+            raise Panic("lwe_dim, glwe_dim and batch must not be negative, pbs_levels, ks_levels and cbs_levels >= 1")
+        return self._fn(name)(self._h, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch)

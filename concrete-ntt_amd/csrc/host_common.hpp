@@ -5,13 +5,15 @@
 // that owns the launch, declared here and explicitly instantiated there.  Nothing declared here is exported.
 // pbs_host.hpp, on top of this file, is the host side of the programmable bootstrap as templates over the plan family, and lwe_host.hpp, on
 // top of that, the host side of the keyswitch, keyswitch + bootstrap and packing keyswitch; multibit_host.hpp, also on top of pbs_host.hpp,
-// the host side of the multi-bit blind rotation and bootstrap: host_native_ext.hip and host_prime.hip (through its host_prime_*.inc) each
+// the host side of the multi-bit blind rotation and bootstrap, and cbs_host.hpp that of the circuit bootstrap and the many-LUT calls:
+// host_native_ext.hip and host_prime.hip (through its host_prime_*.inc) each
 // include them and instantiate them for their plans.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -45,6 +47,17 @@ int fail(int code, const char *fmt, ...);
 inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return abytes && bbytes && x < y + bbytes && y < x + abytes;
+}
+// whether the product of the factors reaches 2^63: taken factor by factor, so that the 128-bit product never wraps.  For the byte counts
+// that are products of a call's arguments: they must fit before they are formed.
+inline bool product_passes_2_63(std::initializer_list<size_t> factors) {
+    u128 x = 1;
+    for (size_t f : factors) {
+        if (f == 0) return false;
+        x *= f;
+        if (x >= ((u128)1 << 63)) return true;
+    }
+    return false;
 }
 struct Operand {
     const char *name;

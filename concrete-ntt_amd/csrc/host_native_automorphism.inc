@@ -32,7 +32,7 @@ static int native_automorphism(const cntt_native *pl, void *out, const void *in,
     if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
     if (int rc = native_autom_check_t(pl, t)) return rc;
     const size_t w = (size_t)pl->info.word;
-    if (cmux_passes_2_63({batch, npolys, pl->n, w}))
+    if (product_passes_2_63({batch, npolys, pl->n, w}))
         return fail(CNTT_EINVAL, "npolys = %zu, batch = %zu: the polynomials pass 2^63 bytes", npolys, batch);
     if (batch == 0 || npolys == 0) return CNTT_OK;
     if (!out) return fail(CNTT_EINVAL, "out is NULL");
@@ -64,7 +64,7 @@ static int native_automorphism_ntt(const cntt_native *pl, void *const *out_plane
     if (int rc = native_autom_check_t(pl, t)) return rc;
     const size_t rb = pl->rbytes();
     const int np = pl->info.nprimes;
-    if (cmux_passes_2_63({batch, npolys, pl->n, rb}))
+    if (product_passes_2_63({batch, npolys, pl->n, rb}))
         return fail(CNTT_EINVAL, "npolys = %zu, batch = %zu: the residue polynomials pass 2^63 bytes", npolys, batch);
     if (batch == 0 || npolys == 0) return CNTT_OK;
     if (!out_planes) return fail(CNTT_EINVAL, "out_planes is NULL");
@@ -163,8 +163,8 @@ static int glwe_autoks(const typename F::Plan *pl, typename F::Word *glwe_out, c
         return fail(CNTT_EINVAL, "batch * max(glwe_dim * levels, glwe_dim + 1) = %zu * %zu is not below 2^32: too large for one launch", batch, launch);
     // the byte counts -- ciphertexts, digits, key -- are products of the arguments: they must fit before they are formed
     const size_t n = pl->n, w = F::word(pl);
-    if (cmux_passes_2_63({batch, k + 1, n, w}) || cmux_passes_2_63({batch, k, levels, n, w}) ||
-        cmux_passes_2_63({(size_t)steps, k, levels, k + 1, n, w}))
+    if (product_passes_2_63({batch, k + 1, n, w}) || product_passes_2_63({batch, k, levels, n, w}) ||
+        product_passes_2_63({(size_t)steps, k, levels, k + 1, n, w}))
         return fail(CNTT_EINVAL, "glwe_dim = %zu, levels = %u, batch = %zu: the ciphertexts, the digits or the key pass 2^63 bytes", k, levels, batch);
     if (batch == 0) return CNTT_OK;
     if (!glwe_out) return fail(CNTT_EINVAL, "glwe_out is NULL");

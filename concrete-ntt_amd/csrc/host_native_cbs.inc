@@ -1,156 +1,82 @@
-// Part of host_native_ext.hip (included at its end, after host_native_cmux.inc): the circuit bootstrap from LWE bits to GGSW selectors
-// (include/cntt_cbs.h) -- the argument checks, the workspace layout, the host-slice path and the C ABI over the kernels of native_cbs.hpp
-// (launched by native_cbs.hip), blind_rotate_device<NativePbs>, native_split_device and native_ntt_device, which it calls and does not
-// change.
+// Part of host_native_ext.hip (included at its end, after host_native_cmux.inc): the native plans' side of the circuit bootstrap from LWE
+// bits to GGSW selectors (include/cntt_cbs.h), of the many-LUT bootstrap and of the circuit bootstrap with one rotation per input bit
+// (include/cntt_manylut.h) -- the members of NativePbs that cbs_host.hpp asks for, over the kernels of native_cbs.hpp and
+// native_manylut.hpp (launched by native_cbs.hip and native_manylut.hip), native_split_device and native_ntt_device, and the C ABI.  The
+// checks, the workspace and the launch sequences are cbs_host.hpp's, shared with the prime plans.
 #include "../../include/cntt_cbs.h"
+#include "../../include/cntt_manylut.h"
 #include "native_cbs.hpp"
+#include "native_manylut.hpp"
 
 #pragma GCC visibility push(hidden)
 
-// the seven parts of the workspace, in bytes and in this order (cntt_cbs.h states the formula)
-struct NativeCbsSizes {
-    size_t rot, table, pbs_digits, acc, ks_digits, part, sel;
-    NativeCbsShape shape;
-    size_t total() const {
-        return up256(rot) + up256(table) + up256(pbs_digits) + up256(acc) + up256(ks_digits) + up256(part) + up256(sel);
-    }
-};
-static NativeCbsSizes native_cbs_sizes(const cntt_native *pl, size_t lwe_dim, size_t k, unsigned pbs_levels, unsigned ks_levels,
-                                       unsigned cbs_levels, size_t batch) {
-    const size_t w = (size_t)pl->info.word, e = batch * cbs_levels, r = (k * pl->n + 1) * ks_levels, ct = (k + 1) * pl->n * w;
-    NativeCbsSizes Z;
-    Z.shape = native_cbs_shape(pl->n, w, k, r, e);
-    Z.rot = (lwe_dim + 1) * e * sizeof(uint32_t);
-    Z.table = e * ct;
-    Z.pbs_digits = e * ct * pbs_levels;
-    Z.acc = e * ct;
-    Z.ks_digits = e * r * sizeof(int32_t);
-    Z.part = Z.shape.slabs * (k + 1) * e * ct;
-    Z.sel = (k + 1) * e * ct;
-    return Z;
-}
-
-// one of the three gadgets: `name` is the prefix of its two arguments; budget: the bits base_log * levels may fill
-static int native_cbs_check_gadget(const char *name, unsigned base_log, unsigned levels, unsigned wbits) {
-    if (base_log == 0) return fail(CNTT_EINVAL, "%sbase_log is 0", name);
-    if (levels == 0) return fail(CNTT_EINVAL, "%slevels is 0", name);
-    if ((uint64_t)base_log * levels > wbits) return fail(CNTT_EINVAL, NativePbs::DIGIT_BUDGET_MSG, name, name, base_log, levels, wbits);
-    return CNTT_OK;
-}
-
-// set-up -> one blind rotation over the E = batch * cbs_levels elements -> extraction and signed digits -> the digit x key product in
-// slabs -> the sum of the slabs, negated, in the selector layout -> the split into residues and the forward transforms, the two steps of
-// cntt_native_fwd_batch, into the caller's planes.  ws holds rot | table | digits of the rotation | acc | int32 digits | slab partials |
-// selector words (NativeCbsSizes).
-static int native_cbs_device(const cntt_native *pl, void *const *out, const void *lwe_in, NativePbs::Key bsk, const void *fpksk, size_t lwe_dim,
-                             size_t k, unsigned pbs_base_log, unsigned pbs_levels, unsigned ks_base_log, unsigned ks_levels,
-                             unsigned cbs_base_log, unsigned cbs_levels, size_t batch, const NativeCbsSizes &Z, char *ws, hipStream_t st) {
-    const size_t e = batch * cbs_levels, n = pl->n, r = (k * n + 1) * ks_levels, polys = e * (k + 1) * (k + 1);
-    const int word = pl->info.word, logn = native_logn(pl);
-    char *at = ws;
-    const auto part_of = [&at](size_t bytes) {
-        char *here = at;
-        at += up256(bytes);
-        return static_cast<void *>(here);
-    };
-    uint32_t *rot_t = static_cast<uint32_t *>(part_of(Z.rot));
-    void *table = part_of(Z.table), *pbs_digits = part_of(Z.pbs_digits), *acc = part_of(Z.acc);
-    int32_t *ks_digits = static_cast<int32_t *>(part_of(Z.ks_digits));
-    void *part = part_of(Z.part), *sel = part_of(Z.sel);
-
-    const NativeCbsConst C{(uint32_t)logn, (uint32_t)k, cbs_base_log, cbs_levels};
-    hipError_t err = launch_native_cbs_setup(word, rot_t, table, lwe_in, C, lwe_dim, e, ew_grid((lwe_dim + 1) * e + Z.table / 16), st);
-    if (err != hipSuccess) return fail(CNTT_EDEVICE, "native_cbs_setup_kernel launch failed: %s", hipGetErrorString(err));
-    if (int rc = blind_rotate_device<NativePbs>(pl, acc, table, true, rot_t, bsk, lwe_dim, k, pbs_base_log, pbs_levels, e, pbs_digits, st)) return rc;
-    const u128 off = gadget_offset(NativePbs::digit_bits(pl), ks_base_log, ks_levels);
-    err = launch_native_cbs_extract(word, ks_digits, acc, (uint64_t)off, (uint64_t)(off >> 64), ks_base_log, ks_levels, C, e,
-                                    ew_grid(e * (k * n + 1)), st);
-    if (err != hipSuccess) return fail(CNTT_EDEVICE, "native_cbs_extract_kernel launch failed: %s", hipGetErrorString(err));
-    err = launch_native_cbs_ks(word, part, ks_digits, fpksk, logn, k, r, e, Z.shape, st);
-    if (err != hipSuccess) return fail(CNTT_EDEVICE, "native_cbs_ks_kernel launch failed: %s", hipGetErrorString(err));
-    err = launch_native_cbs_sum(word, sel, part, logn, k, cbs_levels, e, Z.shape.slabs, ew_grid(Z.sel / 16), st);
-    if (err != hipSuccess) return fail(CNTT_EDEVICE, "native_cbs_sum_kernel launch failed: %s", hipGetErrorString(err));
-    if (int rc = native_split_device(pl, sel, out, polys * n, false, st)) return rc;
-    return native_ntt_device(pl, out, polys, false, st);
-}
-
-static const char *const CBS_OUT[10] = {"ggsw_ntt_out[0]", "ggsw_ntt_out[1]", "ggsw_ntt_out[2]", "ggsw_ntt_out[3]", "ggsw_ntt_out[4]",
-                                        "ggsw_ntt_out[5]", "ggsw_ntt_out[6]", "ggsw_ntt_out[7]", "ggsw_ntt_out[8]", "ggsw_ntt_out[9]"};
-static const char *const CBS_BSK[10] = {"bsk_ntt[0]", "bsk_ntt[1]", "bsk_ntt[2]", "bsk_ntt[3]", "bsk_ntt[4]",
-                                        "bsk_ntt[5]", "bsk_ntt[6]", "bsk_ntt[7]", "bsk_ntt[8]", "bsk_ntt[9]"};
-
-static int native_circuit_bootstrap(const cntt_native *pl, void *const *ggsw_ntt_out, const void *lwe_in, NativePbs::Key bsk_ntt, const void *fpksk,
-                                    size_t lwe_dim, size_t k, unsigned pbs_base_log, unsigned pbs_levels, unsigned ks_base_log, unsigned ks_levels,
-                                    unsigned cbs_base_log, unsigned cbs_levels, size_t batch, void *workspace, size_t workspace_bytes,
-                                    cntt_mem_t where, hipStream_t st) {
-    if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
+int NativePbs::cbs_plan_check(const cntt_native *pl) {
     if (pl->info.binary)
         return fail(CNTT_EINVAL, "plan is of a native_binary kind: a produced selector has full-width words, and the exactness of these kinds rests on "
                                  "0/1 key words");
-    const unsigned wbits = NativePbs::digit_bits(pl);
-    if (int rc = native_cbs_check_gadget("pbs_", pbs_base_log, pbs_levels, wbits)) return rc;
-    if (int rc = native_cbs_check_gadget("ks_", ks_base_log, ks_levels, wbits)) return rc;
-    if (ks_base_log > 31) return fail(CNTT_EINVAL, "ks_base_log = %u is above 31: a signed digit must fit an int32", ks_base_log);
-    if (int rc = native_cbs_check_gadget("cbs_", cbs_base_log, cbs_levels, wbits)) return rc;
+    return CNTT_OK;
+}
+int NativePbs::cbs_budget_check(const cntt_native *pl, unsigned cbs_base_log, unsigned cbs_levels) {
+    const unsigned wbits = digit_bits(pl);
     if ((uint64_t)cbs_base_log * cbs_levels > wbits - 1)
         return fail(CNTT_EINVAL, "cbs_base_log * cbs_levels = %u * %u exceeds w - 1 = %u: H = 2^(w - cbs_base_log * cbs_levels) / 2 must be a word, "
                                  "and 2 has no inverse mod 2^w", cbs_base_log, cbs_levels, wbits - 1);
-    if (native_logn(pl) > NativePbs::MODSWITCH_MAX_LOGN) return fail(CNTT_EINVAL, "ntt_size too large for the modulus switch");
-    if (k + 1 >= ((size_t)1 << 32) || k + 1 == 0) return fail(CNTT_EINVAL, "glwe_dim too large");
-    if (int rc = NativePbs::check_terms(pl, k, pbs_levels)) return rc;
-    const size_t n = pl->n, w = (size_t)pl->info.word, rb = pl->rbytes();
-    if (((u128)k * n + 1) * ks_levels >= ((u128)1 << 32))
-        return fail(CNTT_EINVAL, "(glwe_dim * n + 1) * ks_levels = (%zu * %zu + 1) * %u is not below 2^32 key rows", k, n, ks_levels);
-    const size_t r = (k * n + 1) * ks_levels;
-    // what the widest launches hold: the external product of the rotation over all E = batch * cbs_levels elements, and the transforms of
-    // the selectors' polynomials
-    if ((u128)batch * cbs_levels * (k + 1) * pbs_levels >= ((u128)1 << 32) || (u128)batch * cbs_levels * (k + 1) * (k + 1) * n >= ((u128)1 << 46))
-        return fail(CNTT_EINVAL, "batch * cbs_levels * (glwe_dim + 1) * pbs_levels = %zu * %u * %zu * %u is not below 2^32, or the selectors' words "
-                                 "are not below 2^46: too large for one launch", batch, cbs_levels, k + 1, pbs_levels);
-    const size_t e = batch * cbs_levels;
-    // the byte counts are products of the arguments: they must fit before they are formed (2048 = the most slabs the shape rule gives)
-    if (cmux_passes_2_63({batch, lwe_dim + 1, w}) || lwe_dim + 1 == 0 || cmux_passes_2_63({lwe_dim + 1, e, (size_t)4}) ||
-        cmux_passes_2_63({lwe_dim, k + 1, (size_t)pbs_levels, k + 1, n, rb}) || cmux_passes_2_63({k + 1, r, k + 1, n, w}) ||
-        cmux_passes_2_63({e, k + 1, (size_t)pbs_levels, n, w}) || cmux_passes_2_63({e, r, (size_t)4}) ||
-        cmux_passes_2_63({(size_t)2048, k + 1, e, k + 1, n, w}) || cmux_passes_2_63({k + 1, e, k + 1, n, rb}))
-        return fail(CNTT_EINVAL, "lwe_dim = %zu, glwe_dim = %zu, batch = %zu: the ciphertexts, the keys, the selectors or the workspace pass 2^63 bytes",
-                    lwe_dim, k, batch);
-    if (batch == 0) return CNTT_OK;
-    const int np = pl->info.nprimes;
-    if (!ggsw_ntt_out) return fail(CNTT_EINVAL, "ggsw_ntt_out is NULL");
-    for (int i = 0; i < np; ++i)
-        if (!ggsw_ntt_out[i]) return fail(CNTT_EINVAL, "NULL output residue plane (%s)", CBS_OUT[i]);
-    if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
-    if (lwe_dim)
-        if (int rc = NativePbs::key_check(pl, bsk_ntt, "bsk_ntt")) return rc;
-    if (!fpksk) return fail(CNTT_EINVAL, "fpksk is NULL");
-    const NativeCbsSizes Z = native_cbs_sizes(pl, lwe_dim, k, pbs_levels, ks_levels, cbs_levels, batch);
-    const size_t need = Z.total();
-    if (workspace)
-        if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
-    const size_t ob = e * (k + 1) * (k + 1) * n * rb, ib = batch * (lwe_dim + 1) * w, bb = NativePbs::key_bytes(pl, lwe_dim * (k + 1) * pbs_levels * (k + 1)),
-                 fb = (k + 1) * r * (k + 1) * n * w;
-    Operand ops[23];
-    int cnt = 0;
-    for (int i = 0; i < np; ++i) ops[cnt++] = {CBS_OUT[i], ggsw_ntt_out[i], ob, rb, true};
-    ops[cnt++] = {"lwe_in", lwe_in, ib, w, false};
-    for (int i = 0; i < np && bb; ++i) ops[cnt++] = {CBS_BSK[i], bsk_ntt[i], bb, rb, false};
-    ops[cnt++] = {"fpksk", fpksk, fb, 16, false};   // read in 16-byte vectors
-    ops[cnt++] = {"workspace", workspace, workspace ? workspace_bytes : 0, 16, true};
-    if (int rc = check_operands(ops, cnt)) return rc;
-    Staging s(where, st);
-    NativePbs::KeyStore ks;
-    const void *din = s.in(lwe_in, ib);
-    const NativePbs::Key dbsk = lwe_dim ? NativePbs::key_in(pl, s, bsk_ntt, bb, ks) : NativePbs::Key{};
-    const void *dfk = s.in(fpksk, fb);
-    void *dout[10];
-    for (int i = 0; i < np; ++i) dout[i] = s.out(ggsw_ntt_out[i], ob);
-    char *dws = (char *)s.workspace(workspace, need);   // one block for the whole call
-    if (int rc = s.status()) return rc;
-    if (int rc = native_cbs_device(pl, dout, din, dbsk, dfk, lwe_dim, k, pbs_base_log, pbs_levels, ks_base_log, ks_levels, cbs_base_log, cbs_levels,
-                                   batch, Z, dws, st))
-        return rc;
-    return s.finish();
+    return CNTT_OK;
+}
+// the extraction owns 16 bytes of a row per thread
+int NativePbs::extract_many_check(const cntt_native *pl) {
+    if (pl->n * (size_t)pl->info.word < 16)
+        return fail(CNTT_EINVAL, "ntt_size = %zu words of %d bytes are below the 16 bytes one thread of the extraction owns", pl->n, pl->info.word);
+    return CNTT_OK;
+}
+
+#define CBS_PLANES(s) {s "[0]", s "[1]", s "[2]", s "[3]", s "[4]", s "[5]", s "[6]", s "[7]", s "[8]", s "[9]"}
+static const char *const CBS_OUT[10] = CBS_PLANES("ggsw_ntt_out");
+static const char *const CBS_BSK[10] = CBS_PLANES("bsk_ntt");
+#undef CBS_PLANES
+// how the key and the output appear among the operands: one plane per prime
+int NativePbs::bsk_operands(const cntt_native *pl, Operand *ops, int cnt, Key bsk, size_t kb) {
+    for (int i = 0; i < pl->info.nprimes && kb; ++i) ops[cnt++] = {CBS_BSK[i], bsk[i], kb, pl->rbytes(), false};
+    return cnt;
+}
+int NativePbs::cbs_out_planes(const cntt_native *pl, CbsOut out, void **planes, const char **names) {
+    std::copy(out, out + pl->info.nprimes, planes);
+    std::copy(CBS_OUT, CBS_OUT + pl->info.nprimes, names);
+    return pl->info.nprimes;
+}
+
+hipError_t NativePbs::launch_modswitch_manylut(const cntt_native *pl, uint32_t *rot_t, const void *lwe, unsigned log_lut, size_t lwe_dim,
+                                               size_t batch, unsigned grid, hipStream_t st) {
+    return launch_native_modswitch_manylut(pl->info.word, rot_t, lwe, native_logn(pl), log_lut, lwe_dim, batch, grid, st);
+}
+hipError_t NativePbs::launch_extract_many(const cntt_native *pl, void *lwe_out, const void *glwe, size_t k, size_t count, size_t batch,
+                                          bool stream, unsigned grid, hipStream_t st) {
+    return launch_native_sample_extract_many(pl->info.word, lwe_out, glwe, native_logn(pl), k, count, batch, stream, grid, st);
+}
+hipError_t NativePbs::launch_cbs_setup(const cntt_native *pl, uint32_t *rot_t, void *table, const void *lwe, const CbsConst &C,
+                                       const unsigned *log_lut, size_t lwe_dim, size_t rotations, unsigned grid, hipStream_t st) {
+    if (log_lut) return launch_native_cbs_manylut_setup(pl->info.word, rot_t, table, lwe, C, *log_lut, lwe_dim, rotations, grid, st);
+    return launch_native_cbs_setup(pl->info.word, rot_t, table, lwe, C, lwe_dim, rotations, grid, st);
+}
+hipError_t NativePbs::launch_cbs_extract(const cntt_native *pl, int32_t *digits, const void *acc, unsigned ks_base_log, unsigned ks_levels,
+                                         const CbsConst &C, bool one_rotation, size_t rotations, unsigned grid, hipStream_t st) {
+    const u128 off = gadget_offset(digit_bits(pl), ks_base_log, ks_levels);
+    return (one_rotation ? launch_native_cbs_manylut_extract : launch_native_cbs_extract)(pl->info.word, digits, acc, (uint64_t)off,
+                                                                                          (uint64_t)(off >> 64), ks_base_log, ks_levels, C,
+                                                                                          rotations, grid, st);
+}
+hipError_t NativePbs::launch_cbs_ks(const cntt_native *pl, void *part, const int32_t *digits, const void *fpksk, size_t k, size_t rows,
+                                    size_t elements, const CbsShape &shape, unsigned, hipStream_t st) {
+    return launch_native_cbs_ks(pl->info.word, part, digits, fpksk, native_logn(pl), k, rows, elements, shape, st);
+}
+hipError_t NativePbs::launch_cbs_sum(const cntt_native *pl, void *sel, const void *part, size_t k, unsigned cbs_levels, size_t elements,
+                                     size_t slabs, unsigned grid, hipStream_t st) {
+    return launch_native_cbs_sum(pl->info.word, sel, part, native_logn(pl), k, cbs_levels, elements, slabs, grid, st);
+}
+// the selector words into the caller's planes: the two steps of cntt_native_fwd_batch
+int NativePbs::cbs_finish(const cntt_native *pl, void *const *out, const void *sel, size_t polys, hipStream_t st) {
+    if (int rc = native_split_device(pl, sel, out, polys * pl->n, false, st)) return rc;
+    return native_ntt_device(pl, out, polys, false, st);
 }
 #pragma GCC visibility pop
 
@@ -160,11 +86,41 @@ extern "C" int cntt_native_circuit_bootstrap_batch(const cntt_native_t *pl, void
                                                    unsigned pbs_base_log, unsigned pbs_levels, unsigned ks_base_log, unsigned ks_levels,
                                                    unsigned cbs_base_log, unsigned cbs_levels, size_t batch, void *workspace,
                                                    size_t workspace_bytes, cntt_mem_t where, void *stream) {
-    return native_circuit_bootstrap(pl, ggsw_ntt_out, lwe_in, bsk_ntt, fpksk, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log, ks_levels,
-                                    cbs_base_log, cbs_levels, batch, workspace, workspace_bytes, where, (hipStream_t)stream);
+    return circuit_bootstrap<NativePbs>(pl, ggsw_ntt_out, lwe_in, bsk_ntt, fpksk, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log,
+                                        ks_levels, cbs_base_log, cbs_levels, nullptr, batch, workspace, workspace_bytes, where, (hipStream_t)stream);
 }
 extern "C" size_t cntt_native_circuit_bootstrap_workspace_bytes(const cntt_native_t *pl, size_t lwe_dim, size_t glwe_dim, unsigned pbs_levels,
                                                                 unsigned ks_levels, unsigned cbs_levels, size_t batch) {
-    return pl ? native_cbs_sizes(pl, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch).total() : 0;
+    return cbs_workspace_bytes<NativePbs>(pl, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch, false);
 }
 extern "C" unsigned cntt_native_cbs_grid(size_t items, int logn, size_t word_bytes) { return native_cbs_grid(items, logn, word_bytes); }
+
+extern "C" int cntt_native_lwe_modswitch_manylut_batch(const cntt_native_t *pl, uint32_t *rot_t, const void *lwe, size_t lwe_dim,
+                                                       unsigned log_lut_count, size_t batch, cntt_mem_t where, void *stream) {
+    return lwe_modswitch_manylut<NativePbs>(pl, rot_t, lwe, lwe_dim, log_lut_count, batch, where, (hipStream_t)stream);
+}
+extern "C" int cntt_native_sample_extract_many_batch(const cntt_native_t *pl, void *lwe_out, const void *glwe, size_t glwe_dim, size_t count,
+                                                     size_t batch, cntt_mem_t where, void *stream) {
+    return sample_extract_many<NativePbs>(pl, lwe_out, glwe, glwe_dim, count, batch, where, (hipStream_t)stream);
+}
+extern "C" int cntt_native_bootstrap_manylut_batch(const cntt_native_t *pl, void *lwe_out, const void *lwe_in, const void *lut,
+                                                   int lut_per_element, const void *const *bsk_ntt, size_t lwe_dim, size_t glwe_dim,
+                                                   unsigned base_log, unsigned levels, unsigned log_lut_count, size_t lut_count, size_t batch,
+                                                   void *workspace, size_t workspace_bytes, cntt_mem_t where, void *stream) {
+    return bootstrap_manylut<NativePbs>(pl, lwe_out, lwe_in, lut, lut_per_element, bsk_ntt, lwe_dim, glwe_dim, base_log, levels, log_lut_count,
+                                        lut_count, batch, workspace, workspace_bytes, where, (hipStream_t)stream);
+}
+extern "C" int cntt_native_circuit_bootstrap_manylut_batch(const cntt_native_t *pl, void *const *ggsw_ntt_out, const void *lwe_in,
+                                                           const void *const *bsk_ntt, const void *fpksk, size_t lwe_dim, size_t glwe_dim,
+                                                           unsigned pbs_base_log, unsigned pbs_levels, unsigned ks_base_log, unsigned ks_levels,
+                                                           unsigned cbs_base_log, unsigned cbs_levels, unsigned log_lut_count, size_t batch,
+                                                           void *workspace, size_t workspace_bytes, cntt_mem_t where, void *stream) {
+    return circuit_bootstrap<NativePbs>(pl, ggsw_ntt_out, lwe_in, bsk_ntt, fpksk, lwe_dim, glwe_dim, pbs_base_log, pbs_levels, ks_base_log,
+                                        ks_levels, cbs_base_log, cbs_levels, &log_lut_count, batch, workspace, workspace_bytes, where,
+                                        (hipStream_t)stream);
+}
+extern "C" size_t cntt_native_circuit_bootstrap_manylut_workspace_bytes(const cntt_native_t *pl, size_t lwe_dim, size_t glwe_dim,
+                                                                        unsigned pbs_levels, unsigned ks_levels, unsigned cbs_levels,
+                                                                        size_t batch) {
+    return cbs_workspace_bytes<NativePbs>(pl, lwe_dim, glwe_dim, pbs_levels, ks_levels, cbs_levels, batch, true);
+}

@@ -42,17 +42,6 @@ template <class F> static size_t cmux_tree_workspace_bytes(const typename F::Pla
     return pl ? cmux_tree_sizes<F>(pl, m, k, levels, batch).total() : 0;
 }
 
-// whether the product of the factors reaches 2^63: taken factor by factor, so that the 128-bit product never wraps
-static bool cmux_passes_2_63(std::initializer_list<size_t> factors) {
-    u128 x = 1;
-    for (size_t f : factors) {
-        if (f == 0) return false;
-        x *= f;
-        if (x >= ((u128)1 << 63)) return true;
-    }
-    return false;
-}
-
 // the checks the two calls share; the widest launch holds cts ciphertexts per batch element; sums: whether the call runs an external
 // product at all (a tree of one entry does not)
 template <class F>
@@ -104,7 +93,7 @@ static int glwe_cmux(const typename F::Plan *pl, typename F::Word *glwe_out, con
     if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
     if (int rc = cmux_check_sizes<F>(pl, k, base_log, levels, batch, 1, true)) return rc;
     const size_t n = pl->n, w = F::word(pl);
-    if (cmux_passes_2_63({batch, k + 1, levels, n, w}) || cmux_passes_2_63({k + 1, levels, k + 1, n, w}))
+    if (product_passes_2_63({batch, k + 1, levels, n, w}) || product_passes_2_63({k + 1, levels, k + 1, n, w}))
         return fail(CNTT_EINVAL, "glwe_dim = %zu, levels = %u, batch = %zu: the ciphertexts, the digits or the selector pass 2^63 bytes", k, levels, batch);
     if (batch == 0) return CNTT_OK;
     if (!glwe_out) return fail(CNTT_EINVAL, "glwe_out is NULL");
@@ -168,8 +157,8 @@ static int cmux_tree(const typename F::Plan *pl, typename F::Word *glwe_out, con
     while (((size_t)1 << depth) < m) ++depth;
     const size_t n = pl->n, w = F::word(pl);
     // the byte counts are products of the arguments: they must fit before they are formed
-    if (cmux_passes_2_63({batch, m, n, w}) || cmux_passes_2_63({batch, h, k + 1, levels, n, w}) ||
-        cmux_passes_2_63({(size_t)depth, k + 1, levels, k + 1, n, w}) || cmux_passes_2_63({k + 1, levels, k + 1, n, w}))
+    if (product_passes_2_63({batch, m, n, w}) || product_passes_2_63({batch, h, k + 1, levels, n, w}) ||
+        product_passes_2_63({(size_t)depth, k + 1, levels, k + 1, n, w}) || product_passes_2_63({k + 1, levels, k + 1, n, w}))
         return fail(CNTT_EINVAL, "lut_count = %zu, glwe_dim = %zu, levels = %u, batch = %zu: the table, the ciphertexts, the digits or the selectors pass 2^63 bytes",
                     m, k, levels, batch);
     if (batch == 0) return CNTT_OK;

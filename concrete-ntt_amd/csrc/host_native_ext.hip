@@ -4,17 +4,20 @@
 // LWE-to-GLWE packing keyswitch (include/cntt_pack.h), the multi-bit blind rotation and bootstrap (include/cntt_multibit.h).  The last
 // four are the templates of pbs_host.hpp, lwe_host.hpp and multibit_host.hpp, shared with the prime plans: here are the family struct that
 // fits them to the native plans (NativePbs) and the C ABI over them (the multi-bit part: host_native_multibit.inc).  The CMux and the
-// CMux tree against GGSW selectors (include/cntt_cmux.h) are host_native_cmux.inc, over the same struct, and the circuit bootstrap that
-// makes such selectors from LWE bits (include/cntt_cbs.h) is host_native_cbs.inc.  The ring automorphism, the Galois keyswitch and the trace
+// CMux tree against GGSW selectors (include/cntt_cmux.h) are host_native_cmux.inc, over the same struct; the circuit bootstrap that
+// makes such selectors from LWE bits (include/cntt_cbs.h) and the many-LUT calls (include/cntt_manylut.h) are the templates of
+// cbs_host.hpp, with the struct's members and the C ABI in host_native_cbs.inc.  The ring automorphism, the Galois keyswitch and the trace
 // (include/cntt_automorphism.h) are host_native_automorphism.inc, and ring packing of LWE ciphertexts through them (include/cntt_ring_pack.h) is
 // host_native_ring_pack.inc.
 #include <cstdio>
 
+#include "cbs_host.hpp"
 #include "host_common.hpp"
 #include "lwe_host.hpp"
 #include "multibit_host.hpp"
 #include "native_gadget.hpp"
 #include "native_keyswitch.hpp"
+#include "native_manylut.hpp"
 #include "native_pack.hpp"
 #include "native_pbs.hpp"
 
@@ -197,10 +200,10 @@ static int native_gadget_device(const cntt_native *pl, void *terms, const void *
     });
 }
 
-// What the shared host pipelines (pbs_host.hpp, lwe_host.hpp, multibit_host.hpp) need to know of the native plans: words of 4, 8 or 16
-// bytes behind void pointers, digits of the whole word, and a key of one residue plane per prime.  One struct for the bootstrap, the
-// keyswitch, the packing keyswitch and the multi-bit bootstrap (the name is from its first user), so that the combined call runs the
-// bootstrap's own instantiation of the loop.
+// What the shared host pipelines (pbs_host.hpp, lwe_host.hpp, multibit_host.hpp, cbs_host.hpp) need to know of the native plans: words of
+// 4, 8 or 16 bytes behind void pointers, digits of the whole word, and a key of one residue plane per prime.  One struct for the bootstrap,
+// the keyswitch, the packing keyswitch, the multi-bit bootstrap, the circuit bootstrap and the many-LUT calls (the name is from its first
+// user), so that the combined calls run the bootstrap's own instantiation of the loop.
 #pragma GCC visibility push(hidden)
 struct NativePbs {
     using Plan = cntt_native;
@@ -293,6 +296,39 @@ struct NativePbs {
     static int multibit_key_operands(const cntt_native *pl, Operand *ops, int cnt, Key bsk, size_t kb);
     static int multibit_step(const cntt_native *pl, void *acc, void *digits, char *scratch, const MultibitSizes &Z,
                              const uint32_t *rot_rows, Key key, size_t nterms, size_t npolys, unsigned grouping, size_t batch, hipStream_t st);
+
+    // the circuit bootstrap and the many-LUT calls (cbs_host.hpp); what is only declared: host_native_cbs.inc.  The output is one residue
+    // plane per prime; the sum of the slabs goes to selector words in the workspace (CBS_SEL), which cbs_finish splits and transforms into
+    // the planes, 2^46 words at most; the functional key is in words, read in 16-byte vectors.
+    using CbsConst = NativeCbsConst;
+    using CbsShape = NativeCbsShape;
+    using CbsOut = void *const *;
+    static constexpr auto cbs_shape = native_cbs_shape;
+    static constexpr bool CBS_SEL = true;
+    static constexpr size_t EXTRACT_MANY_ROWS = NEXM_ROWS;
+    static size_t key_word(const cntt_native *pl) { return pl->rbytes(); }   // bytes of one key or output residue
+    static Operand fpksk_operand(const cntt_native *, const void *fpksk, size_t bytes) { return {"fpksk", fpksk, bytes, 16, false}; }
+    static CbsConst cbs_const(const cntt_native *pl, size_t k, unsigned cbs_base_log, unsigned cbs_levels) {
+        return CbsConst{(uint32_t)native_logn(pl), (uint32_t)k, cbs_base_log, cbs_levels};
+    }
+    static int cbs_plan_check(const cntt_native *pl);                                                // no binary kinds
+    static int cbs_budget_check(const cntt_native *pl, unsigned cbs_base_log, unsigned cbs_levels);   // w - 1 bits, not w
+    static int extract_many_check(const cntt_native *pl);                                            // a row holds a 16-byte vector
+    static int bsk_operands(const cntt_native *pl, Operand *ops, int cnt, Key bsk, size_t kb);
+    static int cbs_out_planes(const cntt_native *pl, CbsOut out, void **planes, const char **names);
+    static hipError_t launch_modswitch_manylut(const cntt_native *pl, uint32_t *rot_t, const void *lwe, unsigned log_lut, size_t lwe_dim,
+                                               size_t batch, unsigned grid, hipStream_t st);
+    static hipError_t launch_extract_many(const cntt_native *pl, void *lwe_out, const void *glwe, size_t k, size_t count, size_t batch,
+                                          bool stream, unsigned grid, hipStream_t st);
+    static hipError_t launch_cbs_setup(const cntt_native *pl, uint32_t *rot_t, void *table, const void *lwe, const CbsConst &C,
+                                       const unsigned *log_lut, size_t lwe_dim, size_t rotations, unsigned grid, hipStream_t st);
+    static hipError_t launch_cbs_extract(const cntt_native *pl, int32_t *digits, const void *acc, unsigned ks_base_log, unsigned ks_levels,
+                                         const CbsConst &C, bool one_rotation, size_t rotations, unsigned grid, hipStream_t st);
+    static hipError_t launch_cbs_ks(const cntt_native *pl, void *part, const int32_t *digits, const void *fpksk, size_t k, size_t rows,
+                                    size_t elements, const CbsShape &shape, unsigned ks_base_log, hipStream_t st);
+    static hipError_t launch_cbs_sum(const cntt_native *pl, void *sel, const void *part, size_t k, unsigned cbs_levels, size_t elements,
+                                     size_t slabs, unsigned grid, hipStream_t st);
+    static int cbs_finish(const cntt_native *pl, void *const *out, const void *sel, size_t polys, hipStream_t st);
 };
 #pragma GCC visibility pop
 
@@ -459,7 +495,8 @@ extern "C" int cntt_native_pack_keyswitch_batch(const cntt_native_t *pl, void *g
 #include "host_native_cmux.inc"
 
 // ---------------------------------------------------------------------------------------------
-// the circuit bootstrap from LWE bits to GGSW selectors (include/cntt_cbs.h, native_cbs.hpp)
+// the circuit bootstrap from LWE bits to GGSW selectors, the many-LUT bootstrap and the circuit bootstrap with one rotation per input bit
+// (include/cntt_cbs.h, cntt_manylut.h; native_cbs.hpp, native_manylut.hpp; host side: cbs_host.hpp)
 // ---------------------------------------------------------------------------------------------
 #include "host_native_cbs.inc"
 
@@ -472,8 +509,3 @@ extern "C" int cntt_native_pack_keyswitch_batch(const cntt_native_t *pl, void *g
 // ring packing of LWE ciphertexts through automorphisms (include/cntt_ring_pack.h, native_ring_pack.hpp)
 // ---------------------------------------------------------------------------------------------
 #include "host_native_ring_pack.inc"
-
-// ---------------------------------------------------------------------------------------------
-// the many-LUT bootstrap and the circuit bootstrap with one rotation per input bit (include/cntt_manylut.h, native_manylut.hpp)
-// ---------------------------------------------------------------------------------------------
-#include "host_native_manylut.inc"

@@ -80,7 +80,7 @@ static int glwe_embed(const typename F::Plan *pl, typename F::Word *glwe_out, co
     if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
     if (k + 1 >= ((size_t)1 << 32) || k + 1 == 0) return fail(CNTT_EINVAL, "glwe_dim too large");
     const size_t n = pl->n, w = F::word(pl);
-    if (cmux_passes_2_63({batch, k + 1, n, w})) return fail(CNTT_EINVAL, "glwe_dim = %zu, batch = %zu: the ciphertexts pass 2^63 bytes", k, batch);
+    if (product_passes_2_63({batch, k + 1, n, w})) return fail(CNTT_EINVAL, "glwe_dim = %zu, batch = %zu: the ciphertexts pass 2^63 bytes", k, batch);
     if (batch == 0) return CNTT_OK;
     if (!glwe_out) return fail(CNTT_EINVAL, "glwe_out is NULL");
     if (!lwe_in) return fail(CNTT_EINVAL, "lwe_in is NULL");
@@ -107,7 +107,7 @@ static int glwe_merge(const typename F::Plan *pl, typename F::Word *glwe_out, co
     if (int rc = ring_check_sizes<F>(pl, k, base_log, levels, batch, 1)) return rc;
     // the byte counts -- ciphertexts, digits, key -- are products of the arguments: they must fit before they are formed
     const size_t n = pl->n, w = F::word(pl);
-    if (cmux_passes_2_63({batch, k + 1, n, w}) || cmux_passes_2_63({batch, k, levels, n, w}) || cmux_passes_2_63({k, levels, k + 1, n, w}))
+    if (product_passes_2_63({batch, k + 1, n, w}) || product_passes_2_63({batch, k, levels, n, w}) || product_passes_2_63({k, levels, k + 1, n, w}))
         return fail(CNTT_EINVAL, "glwe_dim = %zu, levels = %u, batch = %zu: the ciphertexts, the digits or the key pass 2^63 bytes", k, levels, batch);
     if (batch == 0) return CNTT_OK;
     if (!glwe_out) return fail(CNTT_EINVAL, "glwe_out is NULL");
@@ -183,8 +183,8 @@ static int ring_pack(const typename F::Plan *pl, typename F::Word *glwe_out, con
     // the byte counts are products of the arguments: they must fit before they are formed (batch * h * (k + 1) < 2^32 and m <= 2 h keep
     // the 128-bit product of the LWE rows itself from wrapping)
     const size_t n = pl->n, w = F::word(pl), logn = (size_t)F::logn(pl);
-    if ((u128)batch * m * ((u128)k * n + 1) * w >= ((u128)1 << 63) || cmux_passes_2_63({batch, h, k + 1, n, w}) ||
-        cmux_passes_2_63({batch, h, k, levels, n, w}) || cmux_passes_2_63({logn, k, levels, k + 1, n, w}))
+    if ((u128)batch * m * ((u128)k * n + 1) * w >= ((u128)1 << 63) || product_passes_2_63({batch, h, k + 1, n, w}) ||
+        product_passes_2_63({batch, h, k, levels, n, w}) || product_passes_2_63({logn, k, levels, k + 1, n, w}))
         return fail(CNTT_EINVAL, "lwe_count = %zu, glwe_dim = %zu, levels = %u, batch = %zu: the ciphertexts, the digits or the keys pass 2^63 bytes", m, k,
                     levels, batch);
     if (batch == 0) return CNTT_OK;

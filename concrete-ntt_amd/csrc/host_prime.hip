@@ -570,7 +570,6 @@ template int external_product_device<uint64_t>(const PrimePlan<uint64_t> *, uint
 #include "host_prime_ring_pack.inc"
 // the CMux and the CMux tree against GGSW selectors mod p (include/cntt_prime_cmux.h)
 #include "host_prime_cmux.inc"
-// the circuit bootstrap from LWE bits to GGSW selectors mod p (include/cntt_prime_cbs.h)
+// the circuit bootstrap from LWE bits to GGSW selectors, the many-LUT bootstrap and the circuit bootstrap with one rotation per input bit
+// mod p (include/cntt_prime_cbs.h, cntt_prime_manylut.h)
 #include "host_prime_cbs.inc"
-// the many-LUT bootstrap and the circuit bootstrap with one rotation per input bit mod p (include/cntt_prime_manylut.h)
-#include "host_prime_manylut.inc"

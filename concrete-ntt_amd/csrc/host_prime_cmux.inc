@@ -25,17 +25,6 @@ template <class T> static size_t cmux_tree_workspace_bytes(const PrimePlan<T> *p
     return pl ? cmux_tree_sizes(pl, m, k, levels, batch).total() : 0;
 }
 
-// whether the product of the factors reaches 2^63: taken factor by factor, so that the 128-bit product never wraps
-static bool cmux_passes_2_63(std::initializer_list<size_t> factors) {
-    u128 x = 1;
-    for (size_t f : factors) {
-        if (f == 0) return false;
-        x *= f;
-        if (x >= ((u128)1 << 63)) return true;
-    }
-    return false;
-}
-
 // the checks the two calls share; the widest launch holds cts ciphertexts per batch element
 template <class T> static int cmux_check_sizes(const PrimePlan<T> *pl, size_t k, unsigned base_log, unsigned levels, size_t batch, size_t cts) {
     if (int rc = gadget_check<PrimePbs<T>>(pl, base_log, levels, CNTT_SRC_PLAIN, nullptr)) return rc;
@@ -68,7 +57,7 @@ static int glwe_cmux(const PrimePlan<T> *pl, T *glwe_out, const T *glwe0, const 
                      unsigned levels, size_t batch, void *workspace, size_t workspace_bytes, cntt_mem_t where, hipStream_t st) {
     if (!pl) return fail(CNTT_EINVAL, "plan is NULL");
     if (int rc = cmux_check_sizes(pl, k, base_log, levels, batch, 1)) return rc;
-    if (cmux_passes_2_63({batch, k + 1, levels, pl->n, sizeof(T)}) || cmux_passes_2_63({k + 1, levels, k + 1, pl->n, sizeof(T)}))
+    if (product_passes_2_63({batch, k + 1, levels, pl->n, sizeof(T)}) || product_passes_2_63({k + 1, levels, k + 1, pl->n, sizeof(T)}))
         return fail(CNTT_EINVAL, "glwe_dim = %zu, levels = %u, batch = %zu: the ciphertexts, the digits or the selector pass 2^63 bytes", k, levels, batch);
     if (batch == 0) return CNTT_OK;
     if (!glwe_out) return fail(CNTT_EINVAL, "glwe_out is NULL");
@@ -127,8 +116,8 @@ static int cmux_tree(const PrimePlan<T> *pl, T *glwe_out, const T *lut_in, const
     unsigned depth = 0;
     while (((size_t)1 << depth) < m) ++depth;
     // the byte counts are products of the arguments: they must fit before they are formed
-    if (cmux_passes_2_63({batch, m, pl->n, sizeof(T)}) || cmux_passes_2_63({batch, h, k + 1, levels, pl->n, sizeof(T)}) ||
-        cmux_passes_2_63({(size_t)depth, k + 1, levels, k + 1, pl->n, sizeof(T)}) || cmux_passes_2_63({k + 1, levels, k + 1, pl->n, sizeof(T)}))
+    if (product_passes_2_63({batch, m, pl->n, sizeof(T)}) || product_passes_2_63({batch, h, k + 1, levels, pl->n, sizeof(T)}) ||
+        product_passes_2_63({(size_t)depth, k + 1, levels, k + 1, pl->n, sizeof(T)}) || product_passes_2_63({k + 1, levels, k + 1, pl->n, sizeof(T)}))
         return fail(CNTT_EINVAL, "lut_count = %zu, glwe_dim = %zu, levels = %u, batch = %zu: the table, the ciphertexts, the digits or the selectors pass 2^63 bytes",
                     m, k, levels, batch);
     if (batch == 0) return CNTT_OK;

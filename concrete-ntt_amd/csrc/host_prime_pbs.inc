@@ -1,9 +1,11 @@
 // Part of host_prime.hip (included at its end; kept apart so that file stays readable): the prime plans' side of the programmable
 // bootstrap (include/cntt_prime_pbs.h) -- the constants and the launch of prime_gadget_kernel (prime_pbs.hpp; launched by prime_pbs.hip),
-// what the shared pipelines (pbs_host.hpp, multibit_host.hpp) need to know of these plans, and the C ABI over the first.  The loop's
+// what the shared pipelines (pbs_host.hpp, multibit_host.hpp, cbs_host.hpp) need to know of these plans, and the C ABI over the first.  The loop's
 // external product is external_product_device above, which it calls and does not change.
 #include "../../include/cntt_prime_pbs.h"
+#include "cbs_host.hpp"
 #include "multibit_host.hpp"
+#include "prime_manylut.hpp"
 #include "prime_pbs.hpp"
 
 #pragma GCC visibility push(hidden)
@@ -54,7 +56,7 @@ static int gadget_device(const PrimePlan<T> *pl, T *terms, const T *polys, const
 }
 
 // What the shared bootstrap pipelines need to know of the prime plans: words of type T, digits of the bit length of p, and a key in one
-// buffer of T.
+// buffer of T.  One struct for the bootstrap, the multi-bit bootstrap, the circuit bootstrap and the many-LUT calls.
 template <class T> struct PrimePbs {
     using Plan = PrimePlan<T>;
     using Word = T;
@@ -102,6 +104,50 @@ template <class T> struct PrimePbs {
     }
     static int multibit_step(const Plan *pl, T *acc, T *digits, char *scratch, const MultibitSizes &Z, const uint32_t *rot_rows, Key key,
                              size_t nterms, size_t npolys, unsigned grouping, size_t batch, hipStream_t st);
+
+    // the circuit bootstrap and the many-LUT calls (cbs_host.hpp); what is only declared: host_prime_cbs.inc.  Every plan has them, the
+    // selector gadget may fill the bit length, the extraction takes any size, the output is one buffer that the sum of the slabs writes
+    // (no selector words, nothing to finish), and the functional key is in the NTT domain like the other keys.
+    using CbsConst = PrimeCbsSetup<T>;
+    using CbsShape = ::CbsShape;
+    using CbsOut = T *;
+    static constexpr auto cbs_shape = prime_cbs_shape;
+    static constexpr bool CBS_SEL = false;
+    static constexpr size_t EXTRACT_MANY_ROWS = EXM_ROWS;
+    static size_t key_word(const Plan *) { return sizeof(T); }   // bytes of one key or output residue
+    static Operand fpksk_operand(const Plan *, const T *fpksk, size_t bytes) { return {"fpksk_ntt", fpksk, bytes, sizeof(T), false}; }
+    static CbsConst cbs_const(const Plan *pl, size_t k, unsigned cbs_base_log, unsigned cbs_levels);
+    static int cbs_plan_check(const Plan *) { return CNTT_OK; }
+    static int cbs_budget_check(const Plan *, unsigned, unsigned) { return CNTT_OK; }
+    static int extract_many_check(const Plan *) { return CNTT_OK; }
+    static int bsk_operands(const Plan *, Operand *ops, int cnt, Key bsk, size_t kb) {
+        ops[cnt++] = {"bsk_ntt", bsk, kb, sizeof(T), false};
+        return cnt;
+    }
+    static int cbs_out_planes(const Plan *, CbsOut out, void **planes, const char **names) {
+        planes[0] = out;
+        names[0] = "ggsw_ntt_out";
+        return 1;
+    }
+    static hipError_t launch_modswitch_manylut(const Plan *pl, uint32_t *rot_t, const T *lwe, unsigned log_lut, size_t lwe_dim, size_t batch,
+                                               unsigned grid, hipStream_t st) {
+        return launch_prime_modswitch_manylut<T>(rot_t, lwe, pl->p, pl->logn, log_lut, lwe_dim, batch, grid, st);
+    }
+    static hipError_t launch_extract_many(const Plan *pl, T *lwe_out, const T *glwe, size_t k, size_t count, size_t batch, bool stream,
+                                          unsigned grid, hipStream_t st) {
+        return launch_prime_sample_extract_many<T>(lwe_out, glwe, pl->p, pl->logn, k, count, batch, stream, grid, st);
+    }
+    static hipError_t launch_cbs_setup(const Plan *pl, uint32_t *rot_t, T *table, const T *lwe, const CbsConst &C, const unsigned *log_lut,
+                                       size_t lwe_dim, size_t rotations, unsigned grid, hipStream_t st);
+    static hipError_t launch_cbs_extract(const Plan *pl, int32_t *digits, const T *acc, unsigned ks_base_log, unsigned ks_levels,
+                                         const CbsConst &C, bool one_rotation, size_t rotations, unsigned grid, hipStream_t st);
+    static hipError_t launch_cbs_ks(const Plan *pl, T *part, const int32_t *digits, const T *fpksk, size_t k, size_t rows, size_t elements,
+                                    const CbsShape &shape, unsigned ks_base_log, hipStream_t st);
+    static hipError_t launch_cbs_sum(const Plan *pl, T *out, const T *part, size_t k, unsigned cbs_levels, size_t elements, size_t slabs,
+                                     unsigned grid, hipStream_t st) {
+        return launch_prime_cbs_sum<T>(out, part, pl->p, pl->logn, k, cbs_levels, elements, slabs, grid, st);
+    }
+    static int cbs_finish(const Plan *, void *const *, const T *, size_t, hipStream_t) { return CNTT_OK; }
 };
 #pragma GCC visibility pop
 

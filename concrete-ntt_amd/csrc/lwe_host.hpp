@@ -17,10 +17,7 @@
 template <class F>
 int ks_check(const typename F::Plan *pl, size_t lwe_dim_in, size_t lwe_dim_out, size_t row_stride, unsigned base_log, unsigned levels,
              const char *pre) {
-    const unsigned wbits = F::digit_bits(pl);
-    if (base_log == 0) return fail(CNTT_EINVAL, "%sbase_log is 0", pre);
-    if (levels == 0) return fail(CNTT_EINVAL, "%slevels is 0", pre);
-    if ((uint64_t)base_log * levels > wbits) return fail(CNTT_EINVAL, F::DIGIT_BUDGET_MSG, pre, pre, base_log, levels, wbits);
+    if (int rc = digits_check<F>(pl, pre, base_log, levels)) return rc;
     if (base_log > 31) return fail(CNTT_EINVAL, "%sbase_log = %u exceeds 31: the keyswitch keeps a digit in one 32-bit register", pre, base_log);
     if (row_stride < lwe_dim_out + 1)
         return fail(CNTT_EINVAL, "row_stride = %zu is below lwe_dim_out + 1 = %zu words", row_stride, lwe_dim_out + 1);

@@ -5,7 +5,7 @@
 // Internal, never installed.  Every function here is a template over a family F, one struct of static members per plan family that supplies
 // what the two differ in and nothing else: NativePbs (host_native_ext.hip) and PrimePbs<T> (host_prime_pbs.inc) show the members.
 // lwe_host.hpp, on top of this file, does the same for the keyswitch, the keyswitch + bootstrap call and the packing keyswitch, and
-// multibit_host.hpp for the multi-bit blind rotation and bootstrap.
+// multibit_host.hpp for the multi-bit blind rotation and bootstrap, and cbs_host.hpp for the circuit bootstrap and the many-LUT calls.
 #pragma once
 #include "host_common.hpp"
 
@@ -13,12 +13,17 @@
 
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// the checks every call with digits shares (DIGIT_BUDGET_MSG takes a prefix for the two names first: lwe_host.hpp has one)
-template <class F> int gadget_check(const typename F::Plan *pl, unsigned base_log, unsigned levels, int mode, const uint32_t *rot) {
+// one gadget: `pre` is the prefix of its two arguments' names ("", or "ks_", "pbs_", "cbs_" where a call has several)
+template <class F> int digits_check(const typename F::Plan *pl, const char *pre, unsigned base_log, unsigned levels) {
     const unsigned wbits = F::digit_bits(pl);
-    if (base_log == 0) return fail(CNTT_EINVAL, "base_log is 0");
-    if (levels == 0) return fail(CNTT_EINVAL, "levels is 0");
-    if ((uint64_t)base_log * levels > wbits) return fail(CNTT_EINVAL, F::DIGIT_BUDGET_MSG, "", "", base_log, levels, wbits);
+    if (base_log == 0) return fail(CNTT_EINVAL, "%sbase_log is 0", pre);
+    if (levels == 0) return fail(CNTT_EINVAL, "%slevels is 0", pre);
+    if ((uint64_t)base_log * levels > wbits) return fail(CNTT_EINVAL, F::DIGIT_BUDGET_MSG, pre, pre, base_log, levels, wbits);
+    return CNTT_OK;
+}
+// the checks every call with digits and a source mode shares
+template <class F> int gadget_check(const typename F::Plan *pl, unsigned base_log, unsigned levels, int mode, const uint32_t *rot) {
+    if (int rc = digits_check<F>(pl, "", base_log, levels)) return rc;
     if (mode != CNTT_SRC_PLAIN && mode != CNTT_SRC_ROTATE && mode != CNTT_SRC_CMUX) return fail(CNTT_EINVAL, "src_mode %d is not a cntt_src_mode_t", mode);
     if (mode != CNTT_SRC_PLAIN && !rot) return fail(CNTT_EINVAL, "rot is NULL and src_mode reads it");
     return CNTT_OK;

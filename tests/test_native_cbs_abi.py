@@ -231,3 +231,37 @@ def test_python_wrappers_panic_on_bad_shapes(P):
         with pytest.raises(Panic):
             pl.circuit_bootstrap_workspace_bytes(*args)
     assert c.untouched()
+
+
+# -- the order of the refusals: of two wrong arguments the earlier check answers ---------------------------------------------------
+@pytest.mark.parametrize("P", [native64.Plan32, native32.Plan32, native128.Plan32, native64.Plan52], ids=["native64", "native32", "native128", "native64_plan52"])
+def test_of_two_wrong_arguments_the_earlier_check_answers(P):
+    c = Case(P)
+    W = 8 * c.plan.WORD
+    big = np.full(1 << 16, POISON, dtype=np.uint64)
+    out_in_big = [big.view(c.plan.res_dtype)[:c.out[0].size]] + c.out[1:]
+    ws_in_big = big.view(np.uint8)[256:256 + c.ws.nbytes]
+    for kw, word in [
+            (dict(plan=None, pbs=(0, 2)), "plan is NULL"),
+            (dict(pbs=(0, 2), ks=(0, 2)), "pbs_base_log is 0"), (dict(pbs=(4, 0), cbs=(0, 2)), "pbs_levels is 0"),
+            (dict(ks=(W // 3 + 1, 3), cbs=(4, 0)), "ks_base_log * ks_levels"),
+            (dict(ks=(32, 1), cbs=(4, 0)), "ks_base_log = 32 is above 31"),
+            (dict(cbs=(W // 2, 2), k=(1 << 32) - 1), "2 has no inverse mod 2^w"),
+            (dict(k=(1 << 32) - 1, batch=1 << 63), "glwe_dim too large"),
+            (dict(batch=1 << 32, lwe_dim=1 << 60), "too large for one launch"),
+            (dict(lwe_dim=1 << 60, out=None), "2^63 bytes"),
+            (dict(out=None, lwe=None), "ggsw_ntt_out is NULL"),
+            (dict(lwe=None, fk=None), "lwe_in is NULL"), (dict(bsk=None, fk=None), "bsk_ntt is NULL"),
+            (dict(fk=None, ws=c.ws, ws_bytes=c.ws.nbytes - 1), "fpksk is NULL"),
+            (dict(out=out_in_big, ws=ws_in_big, ws_bytes=c.ws.nbytes - 1), "workspace_bytes"),
+            (dict(lwe=Raw(c.lwe.ctypes.data + 1), out=out_in_big, ws=ws_in_big), "lwe_in is not")]:
+        assert c.call(**kw) == EINVAL, kw
+        assert word in err(), (kw, err())
+        assert c.untouched() and (big == POISON).all(), kw
+
+
+def test_the_binary_kinds_are_refused_before_the_gadgets():
+    c = Case(native_binary64.Plan32)
+    assert c.call(pbs=(0, 2)) == EINVAL and "native_binary" in err(), err()
+    assert c.call(pbs=(4, 0), cbs=(0, 0), ks=(32, 1)) == EINVAL and "native_binary" in err(), err()
+    assert c.untouched()

@@ -291,3 +291,53 @@ def test_python_wrappers_panic_on_bad_shapes(P):
         with pytest.raises(Panic):
             pl.circuit_bootstrap_manylut_workspace_bytes(*args)
     assert c.untouched()
+
+
+# -- the order of the refusals: of two wrong arguments the earlier check answers ---------------------------------------------------
+@pytest.mark.parametrize("P", [native64.Plan32, native32.Plan32, native128.Plan32, native64.Plan52], ids=["native64", "native32", "native128", "native64_plan52"])
+def test_of_two_wrong_arguments_the_earlier_check_answers(P):
+    c = Case(P)
+    W = 8 * c.plan.WORD
+    big = np.full(1 << 16, POISON, dtype=np.uint64)
+    bigw = big.view(c.dtype)
+    out_in_big = with_plane(c.out, 0, big.view(c.plan.res_dtype)[:c.out[0].size])
+    ws_in_big = big.view(np.uint8)[256:256 + c.ws.nbytes]
+    pws_in_big = big.view(np.uint8)[256:256 + c.pws.nbytes]
+    cases = [
+        (c.modswitch, dict(t=LOGN + 1, lwe_dim=1 << 61), "log_lut_count = 6 exceeds"), (c.modswitch, dict(lwe_dim=1 << 61, rot=None), "2^63 bytes"),
+        (c.modswitch, dict(rot=None, lwe=None), "rot_t is NULL"),
+        (c.extract, dict(count=0, k=1 << 62), "count = 0"), (c.extract, dict(k=1 << 62, ext=None), "2^63 bytes"),
+        (c.extract, dict(ext=None, glwe=None), "lwe_out is NULL"),
+        # the many-LUT bootstrap
+        (c.boot, dict(t=LOGN + 1, count=0), "log_lut_count = 6 exceeds"),
+        (c.boot, dict(count=5, pbs=(0, 2)), "lut_count = 5"), (c.boot, dict(count=0, pbs=(0, 2)), "lut_count = 0"),
+        (c.boot, dict(count=5, lwe_dim=1 << 60), "lut_count = 5"), (c.boot, dict(lwe_dim=1 << 60, pbs=(0, 2)), "2^63 bytes"),
+        (c.boot, dict(pbs=(4, 0), bsk=None), "levels is 0"), (c.boot, dict(bsk=None, ext=None), "bsk_ntt is NULL"),
+        (c.boot, dict(ws=c.pws, ws_bytes=c.pws.nbytes - 1, ext=None), "workspace_bytes"), (c.boot, dict(ext=None, lwe=None), "lwe_out is NULL"),
+        (c.boot, dict(lut=None, ext=bigw[:c.ext.size], ws=pws_in_big), "lut is NULL"),
+        # the one-rotation circuit bootstrap
+        (c.cbs, dict(plan=None, pbs=(0, 2)), "plan is NULL"),
+        (c.cbs, dict(pbs=(0, 2), ks=(0, 2)), "pbs_base_log is 0"), (c.cbs, dict(ks=(32, 1), cbs=(4, 0)), "ks_base_log = 32 is above 31"),
+        (c.cbs, dict(cbs=(W // 2, 2), t=LOGN + 1), "2 has no inverse mod 2^w"), (c.cbs, dict(cbs=(W, 1), t=LOGN + 1), "2 has no inverse mod 2^w"),
+        (c.cbs, dict(t=LOGN + 1, cbs=(1, W - 1)), "log_lut_count = 6 exceeds"),
+        (c.cbs, dict(t=LOGN, cbs=(1, 33)), "exceeds ntt_size / 2") if W - 1 >= 33 else (c.cbs, dict(t=LOGN, k=(1 << 32) - 1), "exceeds ntt_size / 2"),
+        (c.cbs, dict(t=0, k=(1 << 32) - 1), "cbs_levels = 2 exceeds 2^log_lut_count = 1"),
+        (c.cbs, dict(k=(1 << 32) - 1, batch=1 << 63), "glwe_dim too large"),
+        (c.cbs, dict(batch=1 << 32, lwe_dim=1 << 60), "too large for one launch"),
+        (c.cbs, dict(lwe_dim=1 << 60, out=None), "2^63 bytes"),
+        (c.cbs, dict(out=None, lwe=None), "ggsw_ntt_out is NULL"),
+        (c.cbs, dict(lwe=None, fk=None), "lwe_in is NULL"), (c.cbs, dict(bsk=None, fk=None), "bsk_ntt is NULL"),
+        (c.cbs, dict(fk=None, ws=c.ws, ws_bytes=c.ws.nbytes - 1), "fpksk is NULL"),
+        (c.cbs, dict(out=out_in_big, ws=ws_in_big, ws_bytes=c.ws.nbytes - 1), "workspace_bytes"),
+        (c.cbs, dict(lwe=Raw(c.lwe.ctypes.data + 1), out=out_in_big, ws=ws_in_big), "lwe_in is not")]
+    for call, kw, word in cases:
+        assert call(**kw) == EINVAL, (call.__name__, kw)
+        assert word in err(), (call.__name__, kw, err())
+        assert c.untouched() and (big == POISON).all(), (call.__name__, kw)
+
+
+def test_the_binary_kinds_are_refused_before_the_gadgets():
+    c = Case(native_binary64.Plan32)
+    assert c.cbs(pbs=(0, 2)) == EINVAL and "native_binary" in err(), err()
+    assert c.cbs(t=LOGN + 1, cbs=(0, 0), ks=(32, 1)) == EINVAL and "native_binary" in err(), err()
+    assert c.untouched()

@@ -193,3 +193,32 @@ def test_python_wrappers_panic_on_bad_shapes(mod, p):
         with pytest.raises(Panic):
             pl.circuit_bootstrap_workspace_bytes(*args)
     assert c.untouched()
+
+
+# -- the order of the refusals: of two wrong arguments the earlier check answers ---------------------------------------------------
+@pytest.mark.parametrize("bits,p", [(64, P62), (64, PM64), (32, P30), (32, P32)])
+def test_of_two_wrong_arguments_the_earlier_check_answers(bits, p):
+    c = Case(bits, p)
+    W = wbits(p)
+    w = c.dtype().itemsize
+    big = np.full(1 << 16, POISON, dtype=c.dtype)
+    out_in_big = big[:c.out.size]
+    ws_in_big = big.view(np.uint8)[16 * w:16 * w + c.ws.nbytes]
+    for kw, word in [
+            (dict(plan=None, pbs=(0, 2)), "plan is NULL"),
+            (dict(pbs=(0, 2), ks=(0, 2)), "pbs_base_log is 0"), (dict(pbs=(4, 0), cbs=(0, 2)), "pbs_levels is 0"),
+            (dict(ks=(W // 3 + 1, 3), cbs=(4, 0)), "ks_base_log * ks_levels"),
+            (dict(ks=(32, 1), cbs=(4, 0)), "ks_base_log = 32 is above 31") if W >= 32 else (dict(ks=(W + 1, 1), cbs=(4, 0)), "exceeds the bit length"),
+            (dict(cbs=(W // 2 + 1, 2), k=(1 << 32) - 1), "cbs_base_log * cbs_levels"),
+            (dict(k=(1 << 32) - 1, batch=1 << 63), "glwe_dim too large"),
+            (dict(k=1 << 27, batch=1 << 63), "2^32 key rows"),
+            (dict(batch=1 << 32, lwe_dim=1 << 60), "too large for one launch"),
+            (dict(lwe_dim=1 << 60, out=None), "2^63 bytes"),
+            (dict(out=None, lwe=None), "ggsw_ntt_out is NULL"),
+            (dict(lwe=None, fk=None), "lwe_in is NULL"), (dict(bsk=None, fk=None), "bsk_ntt is NULL"),
+            (dict(fk=None, ws=c.ws, ws_bytes=c.ws.nbytes - 1), "fpksk_ntt is NULL"),
+            (dict(out=out_in_big, ws=ws_in_big, ws_bytes=c.ws.nbytes - 1), "workspace_bytes"),
+            (dict(lwe=Raw(c.lwe.ctypes.data + 1), out=out_in_big, ws=ws_in_big), "lwe_in is not")]:
+        assert c.call(**kw) == EINVAL, kw
+        assert word in err(), (kw, err())
+        assert c.untouched() and (big == POISON).all(), kw

@@ -246,3 +246,47 @@ def test_python_wrappers_panic_on_bad_shapes(mod, p):
         with pytest.raises(Panic):
             pl.circuit_bootstrap_manylut_workspace_bytes(*args)
     assert c.untouched()
+
+
+# -- the order of the refusals: of two wrong arguments the earlier check answers ---------------------------------------------------
+@pytest.mark.parametrize("bits,p", [(64, P62), (64, PM64), (32, P30), (32, P32)])
+def test_of_two_wrong_arguments_the_earlier_check_answers(bits, p):
+    c = Case(bits, p)
+    W = wbits(p)
+    w = c.dtype().itemsize
+    big = np.full(1 << 16, POISON, dtype=c.dtype)
+    ws_in_big = big.view(np.uint8)[16 * w:16 * w + c.ws.nbytes]
+    pws_in_big = big.view(np.uint8)[16 * w:16 * w + c.pws.nbytes]
+    cases = [
+        (c.modswitch, dict(t=LOGN + 1, lwe_dim=1 << 61), "log_lut_count = 6 exceeds"), (c.modswitch, dict(lwe_dim=1 << 61, rot=None), "2^63 bytes"),
+        (c.modswitch, dict(rot=None, lwe=None), "rot_t is NULL"),
+        (c.extract, dict(count=0, k=1 << 62), "count = 0"), (c.extract, dict(k=1 << 62, ext=None), "2^63 bytes"),
+        (c.extract, dict(ext=None, glwe=None), "lwe_out is NULL"),
+        # the many-LUT bootstrap
+        (c.boot, dict(t=LOGN + 1, count=0), "log_lut_count = 6 exceeds"),
+        (c.boot, dict(count=5, pbs=(0, 2)), "lut_count = 5"), (c.boot, dict(count=0, pbs=(0, 2)), "lut_count = 0"),
+        (c.boot, dict(count=5, lwe_dim=1 << 60), "lut_count = 5"), (c.boot, dict(lwe_dim=1 << 60, pbs=(0, 2)), "2^63 bytes"),
+        (c.boot, dict(pbs=(4, 0), bsk=None), "levels is 0"), (c.boot, dict(bsk=None, ext=None), "bsk_ntt is NULL"),
+        (c.boot, dict(ws=c.pws, ws_bytes=c.pws.nbytes - 1, ext=None), "workspace_bytes"), (c.boot, dict(ext=None, lwe=None), "lwe_out is NULL"),
+        (c.boot, dict(lut=None, ext=big[:c.ext.size], ws=pws_in_big), "lut is NULL"),
+        # the one-rotation circuit bootstrap
+        (c.cbs, dict(plan=None, pbs=(0, 2)), "plan is NULL"),
+        (c.cbs, dict(pbs=(0, 2), ks=(0, 2)), "pbs_base_log is 0"),
+        (c.cbs, dict(ks=(32, 1), cbs=(4, 0)), "ks_base_log = 32 is above 31") if W >= 32 else (c.cbs, dict(ks=(W + 1, 1), cbs=(4, 0)), "exceeds the bit length"),
+        (c.cbs, dict(cbs=(W // 2 + 1, 2), t=LOGN + 1), "cbs_base_log * cbs_levels"),
+        (c.cbs, dict(t=LOGN + 1, cbs=(1, W)), "log_lut_count = 6 exceeds"),
+        (c.cbs, dict(t=LOGN, cbs=(1, 33)), "exceeds ntt_size / 2") if W >= 33 else (c.cbs, dict(t=LOGN, k=(1 << 32) - 1), "exceeds ntt_size / 2"),
+        (c.cbs, dict(t=0, k=(1 << 32) - 1), "cbs_levels = 2 exceeds 2^log_lut_count = 1"),
+        (c.cbs, dict(k=(1 << 32) - 1, batch=1 << 63), "glwe_dim too large"),
+        (c.cbs, dict(k=1 << 27, batch=1 << 63), "2^32 key rows"),
+        (c.cbs, dict(batch=1 << 32, lwe_dim=1 << 60), "too large for one launch"),
+        (c.cbs, dict(lwe_dim=1 << 60, out=None), "2^63 bytes"),
+        (c.cbs, dict(out=None, lwe=None), "ggsw_ntt_out is NULL"),
+        (c.cbs, dict(lwe=None, fk=None), "lwe_in is NULL"), (c.cbs, dict(bsk=None, fk=None), "bsk_ntt is NULL"),
+        (c.cbs, dict(fk=None, ws=c.ws, ws_bytes=c.ws.nbytes - 1), "fpksk_ntt is NULL"),
+        (c.cbs, dict(out=big[:c.out.size], ws=ws_in_big, ws_bytes=c.ws.nbytes - 1), "workspace_bytes"),
+        (c.cbs, dict(lwe=Raw(c.lwe.ctypes.data + 1), out=big[:c.out.size], ws=ws_in_big), "lwe_in is not")]
+    for call, kw, word in cases:
+        assert call(**kw) == EINVAL, (call.__name__, kw)
+        assert word in err(), (call.__name__, kw, err())
+        assert c.untouched() and (big == POISON).all(), (call.__name__, kw)
